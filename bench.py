@@ -1,6 +1,7 @@
 """bench.py -- reconstructions/sec of the multi-t DDPM reconstruction hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg1|cfg2|cfg3|cfg4|cfg5] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--config cfg1|cfg2|cfg3|cfg4|cfg5] [--scaling weak|strong] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -30,10 +31,17 @@ and the per-rank device list gathered over that group.
     cfg5  128^3 volumes, README VQ-VAE (4 x stride 2, 256 ch, 2 048 codes) -> [128, 8, 8, 8] latents -> 3-D
           `small` UNet -> re-quantise + decode -> 2.5-D LPIPS  (batch 64, k = 4)
 
-One JSON line on rank 0.
+One JSON line on rank 0.  A plain run sets up, runs the untimed start-up pass and the --warmup steps, times --steps steps and
+prints the line: `value` (reconstructions/s over the timed steps), `ms_per_step`, `dtype` and the configuration.  Everything
+else below -- `roofline`, `rooflines`, `kernels`, `value_fp32_products`, `value_batch256`, `cpu_baseline`, `per_rank`,
+`value_dataset_scale` -- is measured only under --full.
+--dump-outputs DIR  after the timed steps, rank 0 writes the scores the last timed step returned, in the order of its rows, as
+            DIR/perceptual_difference.npy, DIR/mse.npy and DIR/t.npy (float64; above 64 MB a fixed seeded sample of the
+            rows, whose indices go to DIR/row_index.npy).
+            Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 `dtype`     "f32 (split-f16 MFMA products, fp32 accumulate)": storage, transforms, reductions and accumulation are fp32;
             the MFMA products of the 3x3 / 1x1 convolutions and of attention are rebuilt from exact f16 partial products
-            (`arithmetic` spells it out).  `value_fp32_products` (N = 1, cfg2) is the same workload with every split-f16
+            (`arithmetic` spells it out).  `value_fp32_products` (--full, N = 1, cfg2) is the same workload with every split-f16
             family switched to its fp32-MFMA form (ddpm_set_split_f16(0): bit-exact fp32 products), one timed step after
             the main timed region -- so the line carries both arithmetics.
 `roofline`  the kernel class with the most time in the sampled launches (first UNet step -- and, for the LDM, the decode
@@ -315,6 +323,25 @@ def write_vqvae(run_root, cfg):
     return str(d / "checkpoint.pth")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_KEYS = ("perceptual_difference", "mse", "t")
+
+
+def dump_outputs(out_dir: Path, rows):
+    """The score rows one timed step returns, one float64 array per column in row order; above DUMP_LIMIT_BYTES a fixed
+    seeded sample of the rows (sorted, so the order survives) -- its indices go to row_index.npy."""
+    import numpy as np
+
+    n = len(rows)
+    keep = DUMP_LIMIT_BYTES // (8 * (len(DUMP_KEYS) + 1))
+    idx = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k in DUMP_KEYS:
+        np.save(out_dir / f"{k}.npy", np.array([rows[i][k] for i in idx], dtype=np.float64))
+    if n > keep:
+        np.save(out_dir / "row_index.npy", idx.astype(np.float64))
+
+
 def self_launch(n: int):
     """`python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU, rendezvous on
     127.0.0.1 at a free port) and pass their output through; the exit code is the launcher's."""
@@ -341,18 +368,25 @@ def main():
                     help="default: strong for --gpus > 1 (fixed image set split over the ranks), weak for 1")
     ap.add_argument("--images", type=int, default=None,
                     help="--scaling strong: size of the fixed image set (default: one batch of the config)")
-    ap.add_argument("--no-batch256", action="store_true", help="skip the extra batch-256 measurement (cfg2, N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: in-situ kernel profile and rooflines of the last "
+                         "timed step, the fp32-products and batch-256 legs, the CPU baseline, per-rank timing, the dataset-scale pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-batch256", action="store_true", help="--full: skip the extra batch-256 measurement (cfg2, N = 1)")
     ap.add_argument("--no-fp32-products", action="store_true",
-                    help="skip the extra step on the fp32-MFMA kernels (`value_fp32_products`; cfg2, N = 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: skip the extra step on the fp32-MFMA kernels (`value_fp32_products`; cfg2, N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (cfg2, N = 1)")
     ap.add_argument("--no-dataset-scale", action="store_true",
-                    help="N > 1, strong scaling: skip the extra pass over a --dataset-images set (`value_dataset_scale`)")
+                    help="--full, N > 1, strong scaling: skip the extra pass over a --dataset-images set (`value_dataset_scale`)")
     ap.add_argument("--dataset-images", type=int, default=10000,
-                    help="N > 1, strong scaling: size of the dataset-scale image set (default: the FashionMNIST / CIFAR10 test split)")
+                    help="--full, N > 1, strong scaling: size of the dataset-scale image set (default: the FashionMNIST / CIFAR10 test split)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.cpu_baseline_worker:
         return cpu_baseline_worker()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[a.config]
     batch = a.batch or cfg["batch"]
     if a.scaling is None:
@@ -430,7 +464,7 @@ def main():
         t0 = time.perf_counter()
         gather_ms = []
         for i in range(a.steps):
-            rows = step(profile=(i == a.steps - 1))
+            rows = step(profile=a.full and i == a.steps - 1)
             gather_ms.append(rec.last_stats.get("gather_ms", 0.0))
         torch.cuda.synchronize()
         own_s = time.perf_counter() - t0  # this rank's own work (its last gather waited for the slowest rank)
@@ -454,10 +488,15 @@ def main():
         gathered = [None] * world
         dist.all_gather_object(gathered, devices[0])
         devices = gathered
+    n_t = len({r["t"] for r in rows})
+    assert len(rows) == n_images * n_t, (len(rows), n_images, n_t)  # every rank's scores came back through the gather
+    if a.dump_outputs and rank == 0:
+        dump_outputs(Path(a.dump_outputs), rows)
+        log(f"outputs of the last timed step written to {a.dump_outputs}")
 
     # the same workload at the reference's default batch (reconstruct.py:91), two timed steps
     b256 = None
-    if world == 1 and a.config == "cfg2" and batch != 256 and not a.no_batch256:
+    if a.full and world == 1 and a.config == "cfg2" and batch != 256 and not a.no_batch256:
         sys.stdout = open(os.devnull, "w")
         try:
             l256 = get_data_loader(f"synthetic:blobs:n=256:size={cfg['size']}:channels={cfg['channels']}:seed=0",
@@ -477,7 +516,7 @@ def main():
 
     # the same workload with bit-exact fp32 MFMA products everywhere (the run-time switch of the numeric guard): one timed step
     fp32p = None
-    if world == 1 and a.config == "cfg2" and not a.no_fp32_products:
+    if a.full and world == 1 and a.config == "cfg2" and not a.no_fp32_products:
         from ddpm_ood_amd import _lib as L
 
         sys.stdout = open(os.devnull, "w")
@@ -500,7 +539,7 @@ def main():
 
     # N > 1: what each rank spent where (the driver computes the efficiency; these make its curve diagnosable)
     per_rank_timing = None
-    if world > 1:
+    if a.full and world > 1:
         mine = {"rank": rank, "images": per_rank[rank], "startup_s": round(startup_s, 2), "first_pass_s": round(first_pass_s, 2),
                 "timed_s": round(own_s, 3), "gather_ms_per_step": [round(g, 2) for g in gather_ms]}
         per_rank_timing = [None] * world
@@ -511,7 +550,7 @@ def main():
     # timed pass.  The default --images (one batch of 1 024) leaves a rank 1 024 / N images -- the sub-chip batches of the kernels'
     # worst case -- which no run over a real dataset would see; both numbers are on the line.
     ds_scale = None
-    if world > 1 and a.scaling == "strong" and a.config in ("cfg2", "cfg3") and not a.no_dataset_scale:
+    if a.full and world > 1 and a.scaling == "strong" and a.config in ("cfg2", "cfg3") and not a.no_dataset_scale:
         sys.stdout = open(os.devnull, "w")
         try:
             n_ds = a.dataset_images
@@ -536,16 +575,8 @@ def main():
                     "note": "same strong-scaling split over an image set of the reference's dataset scale; one timed pass, max over ranks"}
         log(f"dataset-scale pass done: {ds_scale}")
 
-    n_t = len({r["t"] for r in rows})
-    assert len(rows) == n_images * n_t, (len(rows), n_images, n_t)  # every rank's scores came back through the gather
     recon_per_step = n_images * n_t
     value = recon_per_step * a.steps / dt
-
-    buf = ctypes.create_string_buffer(1 << 16)
-    n = lib.ddpm_prof_report(buf, len(buf))
-    prof = json.loads(buf.value.decode()) if n > 0 else {}
-    rooflines = rooflines_of(prof, batch)
-    dominant = max(rooflines.values(), key=lambda r: r["ms_in_sample"]) if rooflines else None
 
     line = {
         "metric": f"reconstructions/sec (whole node), {cfg['metric_tag']}", "value": round(value, 3),
@@ -563,15 +594,20 @@ def main():
                        if os.environ.get("DDPM_LPIPS_ALL_VIEWS", "0") == "1" else
                        "last of 3 (the reference's loop overwrites the other two: same scores)"}
                       if cfg.get("spatial") == 3 else {})},
-        "roofline": dominant,
-        "rooflines": {k: {kk: r[kk] for kk in ("bound", "achieved", "unit", "frac", "algorithmic_equiv_tflops",
-                                                "avg_launch_ms", "launches_timed", "ms_in_sample", "algorithmic_GBps")}
-                      for k, r in rooflines.items()},
-        "kernels": {k: {"launches": v["launches"], "ms": round(v["ms"], 3),
-                        "TFLOPs": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else None,
-                        "GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None}
-                    for k, v in prof.items()},
     }
+    if a.full:  # the in-situ profile of the last timed step
+        buf = ctypes.create_string_buffer(1 << 16)
+        n = lib.ddpm_prof_report(buf, len(buf))
+        prof = json.loads(buf.value.decode()) if n > 0 else {}
+        rooflines = rooflines_of(prof, batch)
+        line["roofline"] = max(rooflines.values(), key=lambda r: r["ms_in_sample"]) if rooflines else None
+        line["rooflines"] = {k: {kk: r[kk] for kk in ("bound", "achieved", "unit", "frac", "algorithmic_equiv_tflops",
+                                                       "avg_launch_ms", "launches_timed", "ms_in_sample", "algorithmic_GBps")}
+                             for k, r in rooflines.items()}
+        line["kernels"] = {k: {"launches": v["launches"], "ms": round(v["ms"], 3),
+                               "TFLOPs": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else None,
+                               "GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None}
+                           for k, v in prof.items()}
     line["numeric_guard"] = {k: main_stats.get(k, 0) for k in ("batches_rerun_fp32", "batches_nonfinite")}
     if per_rank_timing:
         line["per_rank"] = per_rank_timing
@@ -584,7 +620,7 @@ def main():
     if fp32p:
         line["value_fp32_products"] = fp32p["value"]
         line["fp32_products"] = fp32p
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "cfg2":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "cfg2":
         line["cpu_baseline"] = cpu_baseline()
         log(f"cpu baseline done: {line['cpu_baseline']}")
     if world > 1:

@@ -177,7 +177,7 @@ def test_bench_self_launches_eight_ranks_on_one_gpu(device):
     env = dict(os.environ, DDPM_DIST_BACKEND="gloo", DDPM_DIST_SHARED_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--images", "64",
-                          "--batch", "8", "--no-cpu-baseline", "--dataset-images", "96"], env=env, capture_output=True, text=True, timeout=1500)
+                          "--batch", "8", "--full", "--no-cpu-baseline", "--dataset-images", "96"], env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -205,7 +205,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu(device):
     env = dict(os.environ, DDPM_DIST_BACKEND="gloo", DDPM_DIST_SHARED_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "32",
-                          "--images", "64", "--no-dataset-scale"], env=env, capture_output=True, text=True, timeout=1500)
+                          "--images", "64", "--full", "--no-dataset-scale"], env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

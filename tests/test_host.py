@@ -47,7 +47,19 @@ def test_product_scheduler_host_logic_equals_oracle():
     assert torch.equal(h.timesteps, o.timesteps) and torch.equal(h.alphas_cumprod, o.alphas_cumprod)
     z = np.load(G / "schedule.npz")
     got = np.asarray([h.plms_coefficients(t, t - 10)[:3] for t in range(0, 1000, 10)], dtype=np.float32)
-    assert np.array_equal(got, z["scaled_plms_coef"])
+
+    def oracle_coef(t):  # the reference's _get_prev_sample scalars, as tests/golden/make_golden.py records them
+        a_t, a_p = o.alphas_cumprod[t], o.alphas_cumprod[t - 10] if t >= 10 else o.final_alpha_cumprod
+        return [float((a_p / a_t) ** 0.5), float(a_p - a_t), float(a_t * (1 - a_p) ** 0.5 + (a_t * (1 - a_t) * a_p) ** 0.5)]
+
+    # bit for bit: the oracle's fp32 0-d tensor arithmetic on this host
+    assert np.array_equal(got, np.asarray([oracle_coef(t) for t in range(0, 1000, 10)], dtype=np.float32))
+    # the committed values were recorded on another CPU, and torch's fp32 CPU kernels (linspace of the beta table, the 0-d
+    # arithmetic) round differently from CPU to CPU: equal to a few ulps of the operands (column 1 is a_p - a_t)
+    want = z["scaled_plms_coef"].astype(np.float64)
+    a_p = z["scaled_alphas_cumprod"][[max(t - 10, 0) for t in range(0, 1000, 10)]].astype(np.float64)
+    tol = 4 * np.finfo(np.float32).eps * np.stack([np.abs(want[:, 0]), a_p, np.abs(want[:, 2])], axis=1)
+    assert (np.abs(got - want) <= tol).all(), np.abs(got - want).max(axis=0)
     # the scheduler surface the reference exercises: reversed(), mask indexing, iteration of 0-d tensors
     starts = reversed(h.timesteps)[1::64]
     assert [int(t) for t in starts] == [10, 650]
@@ -484,6 +496,28 @@ def test_bench_launches_its_own_ranks(monkeypatch):
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node=4" in cmd and "--nnodes=1" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"]
     assert bench.shard_sizes("strong", 8, 1024, 1024) == (1024, [128] * 8)  # the default strong set: one batch over the ranks
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 array per score column in row order; above the size limit a fixed seeded sample of the rows,
+    in order, with its row indices."""
+    import bench
+
+    rows = [{"filename": f"img_{i % 5}", "type": "val", "t": 10 * (i // 5), "perceptual_difference": 0.5 * i, "mse": 1e-3 * i}
+            for i in range(40)]
+    bench.dump_outputs(tmp_path / "all", rows)
+    for k, want in (("perceptual_difference", 0.5), ("mse", 1e-3)):
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == np.float64 and a.tolist() == [want * i for i in range(40)]
+    assert np.load(tmp_path / "all" / "t.npy").tolist() == [10.0 * (i // 5) for i in range(40)]
+    assert not (tmp_path / "all" / "row_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 4 * 16)  # room for 16 rows of the 3 columns + the row index
+    for d in ("s1", "s2"):
+        bench.dump_outputs(tmp_path / d, rows)
+    idx = np.load(tmp_path / "s1" / "row_index.npy")
+    assert len(idx) == 16 and (np.diff(idx) > 0).all() and np.array_equal(idx, np.load(tmp_path / "s2" / "row_index.npy"))
+    assert np.load(tmp_path / "s1" / "mse.npy").tolist() == [1e-3 * int(i) for i in idx]
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) < 8 * 4 * 16 + 4 * 256  # + the .npy headers
 
 
 def test_png_and_pnm_ingest(tmp_path):

@@ -6,11 +6,11 @@ export TMPDIR=/tmp
 o=gpurun_out/r05; mkdir -p $o
 python -m pytest tests -m gpu -q --durations=15 2>&1 | tail -28 > $o/gpu_tests_final.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids > $o/smoke_final.log
-python bench.py --steps 3 --warmup 1 > $o/bench_cfg2.json 2> $o/bench_cfg2.err
-python bench.py --config cfg1 --steps 20 --warmup 5 > $o/bench_cfg1.json 2> $o/bench_cfg1.err
-python bench.py --config cfg3 --steps 1 --warmup 1 > $o/bench_cfg3.json 2> $o/bench_cfg3.err
-python bench.py --config cfg4 --steps 1 --warmup 1 > $o/bench_cfg4.json 2> $o/bench_cfg4.err
-python bench.py --config cfg5 --steps 1 --warmup 0 > $o/bench_cfg5.json 2> $o/bench_cfg5.err
+python bench.py --full --steps 3 --warmup 1 > $o/bench_cfg2.json 2> $o/bench_cfg2.err
+python bench.py --full --config cfg1 --steps 20 --warmup 5 > $o/bench_cfg1.json 2> $o/bench_cfg1.err
+python bench.py --full --config cfg3 --steps 1 --warmup 1 > $o/bench_cfg3.json 2> $o/bench_cfg3.err
+python bench.py --full --config cfg4 --steps 1 --warmup 1 > $o/bench_cfg4.json 2> $o/bench_cfg4.err
+python bench.py --full --config cfg5 --steps 1 --warmup 0 > $o/bench_cfg5.json 2> $o/bench_cfg5.err
 python bench.py --batch 128 --steps 1 --warmup 1 --no-cpu-baseline --no-batch256 --no-fp32-products > $o/bench_cfg2_b128.json 2> $o/bench_cfg2_b128.err
 # kernel trace of the default bench (batch 1 024)
 rocprofv3 --kernel-trace --stats -d $o/prof_kt -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-batch256 --no-fp32-products > $o/bench_b1024_under_rocprofv3.json 2> $o/bench_b1024_under_rocprofv3.err
