@@ -184,6 +184,8 @@ SIGNATURES = {
     "ddpm_mse_loss_grad_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_float, C.c_void_p]),
     "ddpm_fill_f32": (C.c_int, [C.c_void_p, C.c_float, C.c_int64, C.c_void_p]),
     "ddpm_randn_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "ddpm_simplex_noise_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "ddpm_adam_step_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p]),
 }
 

@@ -744,3 +744,35 @@ def vq_nearest(x, codebook):
     check(lib.ddpm_vq_nearest_f32(ptr(x), ptr(e), ptr(norms), idx.data_ptr(), ptr(out), B, D, S, K, stream_ptr()),
           "vq_nearest")
     return idx.long(), out
+
+
+# ---- simplex noise (src/utils/simplex_noise.py: generate_simplex_noise) ----------------------------------
+
+def simplex_noise(shape, seeds, t, octaves: int = 6, persistence: float = 0.8, frequency: float = 64.0, device=None):
+    """AnoDDPM fractal simplex noise of shape [B, C, H, W] or [B, C, D, H, W] (a 3-D input repeats the 2-D slice along D,
+    as the reference does): slice (b, c) is seeded by seeds[b, c] and taken at time t[b].  seeds: int64 [B, C], t: int64 [B],
+    either on the host (they travel in ONE non-blocking copy) or already on the device.  Returns fp32 on the current stream."""
+    lib = _lib.load()
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (4, 5):
+        raise ValueError(f"simplex_noise: shape {shape} is neither [B, C, H, W] nor [B, C, D, H, W]")
+    B, Cn = shape[:2]
+    depth = shape[2] if len(shape) == 5 else 1
+    seeds = torch.as_tensor(seeds, dtype=torch.int64)
+    t = torch.as_tensor(t, dtype=torch.int64)
+    if tuple(seeds.shape) != (B, Cn) or tuple(t.shape) != (B,):
+        raise ValueError(f"simplex_noise: seeds {tuple(seeds.shape)} / t {tuple(t.shape)} do not fit {shape}")
+    if device is None:
+        device = seeds.device if seeds.is_cuda else t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("simplex_noise runs on a ROCm device: the HIP path has no CPU fallback")
+    if seeds.device != device and t.device != device:  # both from the host: one pinned buffer, one copy
+        both = torch.cat([seeds.reshape(-1), t]).pin_memory().to(device, non_blocking=True)
+        seeds_d, t_d = both[: B * Cn], both[B * Cn:]
+    else:
+        seeds_d, t_d = (v.pin_memory().to(device, non_blocking=True) if v.device != device else v.contiguous() for v in (seeds, t))
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    check(lib.ddpm_simplex_noise_f32(ptr(out), seeds_d.data_ptr(), t_d.data_ptr(), B, Cn, depth, shape[-2], shape[-1],
+                                     int(octaves), float(persistence), float(frequency), stream_ptr()), "simplex_noise")
+    return out

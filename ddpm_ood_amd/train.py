@@ -37,10 +37,11 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
+from . import ops
 from . import train_ops as T
 from .data import get_data_loader
 from .train_native import NativeUNetStep, native_supported
-from .trainer import BaseTrainer
+from .trainer import BaseTrainer, simplex_seeds
 
 
 # ---- differentiable forward over the parameter holders ------------------------------------
@@ -169,13 +170,23 @@ class DDPMTrainer(BaseTrainer):
             b = images.shape[0]
             timesteps = torch.randint(0, self.scheduler.num_train_timesteps, (b,), device=self.device,
                                       generator=self.gen).long()
-            noise = torch.randn(images.shape, device=self.device, generator=self.gen)
+            if self.simplex_noise:  # the native step's draw counter and seeds: the same step sees the same noise on both routes
+                self.noise_calls += 1
+                noise = self._simplex(images.shape, timesteps)
+            else:
+                noise = torch.randn(images.shape, device=self.device, generator=self.gen)
             noisy = self.scheduler.add_noise(original_samples=images.contiguous(), noise=noise, timesteps=timesteps,
                                              b_scale=self.b_scale)
         with torch.autocast("cuda", dtype=torch.float16, enabled=self.amp):
             pred = unet_forward_torch(self.model, noisy, timesteps)
             # the reference regresses onto the noise whatever --prediction_type says (ddpm_trainer.py:99-100)
             return F.mse_loss(pred.float(), noise.float())
+
+    def _simplex(self, shape, timesteps: torch.Tensor) -> torch.Tensor:
+        """--simplex_noise (ddpm_trainer.py:93-96, :153-156): slice (row, channel) seeded by (seed, rank, draw counter, row,
+        channel), at the row's timestep."""
+        seeds = simplex_seeds(self.seed * 7919 + self.rank, range(shape[0]), self.noise_calls, shape[1])
+        return ops.simplex_noise(shape, seeds, timesteps, device=self.device)
 
     @torch.no_grad()
     def _loss_native(self, images: torch.Tensor, backward: bool) -> torch.Tensor:
@@ -185,7 +196,10 @@ class DDPMTrainer(BaseTrainer):
         b = images.shape[0]
         timesteps = torch.randint(0, self.scheduler.num_train_timesteps, (b,), generator=self.host_gen).long()
         self.noise_calls += 1
-        noise = T.randn(tuple(images.shape), self.device, self.seed * 7919 + self.rank, self.noise_calls)
+        if self.simplex_noise:
+            noise = self._simplex(images.shape, timesteps)
+        else:
+            noise = T.randn(tuple(images.shape), self.device, self.seed * 7919 + self.rank, self.noise_calls)
         noisy = self.scheduler.add_noise(original_samples=images, noise=noise, timesteps=timesteps, b_scale=self.b_scale)
         t_dev = timesteps.to(self.device)
         if backward:

@@ -26,6 +26,7 @@ import sys
 import time
 from pathlib import Path
 
+import numpy as np
 import pandas as pd
 import torch
 import torch.distributed as dist
@@ -55,6 +56,30 @@ def image_noise(seed: int, index: int, t_start: int, shape) -> torch.Tensor:
 
 def batch_noise(seed: int, indices, t_start: int, shape) -> torch.Tensor:
     return torch.stack([image_noise(seed, i, t_start, shape[1:]) for i in indices])
+
+
+SIMPLEX_SEED_RANGE = 10**10  # Simplex_CLASS.newSeed draws np.random.randint(-10**10, 10**10)
+_U64 = (1 << 64) - 1
+
+
+def _splitmix64(x: np.ndarray) -> np.ndarray:
+    """SplitMix64's finaliser over a uint64 array (wrapping arithmetic)."""
+    x = x + np.uint64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def simplex_seeds(seed: int, indices, t_start: int, channels: int) -> torch.Tensor:
+    """The permutation seeds of --simplex_noise: int64 [len(indices), channels] in the reference's range [-10^10, 10^10), a pure
+    function of (seed, global image index, t_start, channel) -- like image_noise, independent of batch composition and rank
+    count.  (The reference draws them from numpy's global generator in the order its loops meet them.)"""
+    idx = np.asarray([int(i) & _U64 for i in indices], dtype=np.uint64)
+    h = _splitmix64(np.full(idx.shape, int(seed) & _U64, dtype=np.uint64))
+    h = _splitmix64(h ^ idx)
+    h = _splitmix64(h ^ np.uint64(int(t_start) & _U64))
+    h = _splitmix64(h[:, None] ^ np.arange(channels, dtype=np.uint64)[None, :])
+    return torch.from_numpy((h % np.uint64(2 * SIMPLEX_SEED_RANGE)).astype(np.int64) - SIMPLEX_SEED_RANGE)
 
 
 def snr_shift_tables(scheduler, snr_shift: float) -> None:
@@ -222,9 +247,7 @@ class BaseTrainer:
         if self.snr_shift != 1:
             print("Changing scheduler parameters to shift SNR")
             snr_shift_tables(self.scheduler, self.snr_shift)
-        self.simplex_noise = bool(args.simplex_noise)
-        if self.simplex_noise:
-            raise NotImplementedError("--simplex_noise is off the path (default 0, in no BASELINE config)")
+        self.simplex_noise = bool(args.simplex_noise)  # AnoDDPM simplex noise instead of Gaussian (ops.simplex_noise)
 
     def _setup_geometry(self, args):
         """Spatial bookkeeping (base.py:118-131): dimension, resize target, latent padding and its inverse."""
@@ -425,7 +448,11 @@ class Reconstruct(BaseTrainer):
             if self.reset_scheduler_per_t:
                 sched.set_timesteps(self.num_inference_steps)
             start_timesteps = torch.Tensor([t_start] * B).long()
-            noise = batch_noise(self.seed, idx, int(t_start), images.shape).to(self.device, non_blocking=True)
+            if self.simplex_noise:  # reconstruct.py:133-139: T = t_start for every row; the (padded) latent's shape
+                noise = ops.simplex_noise(images.shape, simplex_seeds(self.seed, idx, int(t_start), images.shape[1]),
+                                          start_timesteps, device=self.device)
+            else:
+                noise = batch_noise(self.seed, idx, int(t_start), images.shape).to(self.device, non_blocking=True)
             x = sched.add_noise(original_samples=images, noise=noise, timesteps=start_timesteps,
                                 b_scale=self.b_scale)
             first = self.profile_first_steps

@@ -592,6 +592,13 @@ int ddpm_fill_f32(float *out, float value, int64_t n, ddpm_stream_t stream);
  * of (seed, stream_id, element index).  Not torch's generator stream -- the noise of a training step only has to be
  * reproducible.  */
 int ddpm_randn_f32(float *out, int64_t n, uint64_t seed, uint64_t stream_id, ddpm_stream_t stream);
+/* AnoDDPM fractal simplex noise, the --simplex_noise alternative to Gaussian noise (reference: src/utils/simplex_noise.py,
+ * generate_simplex_noise): out[r, c, d, y, x] = sum over octaves k < octaves of persistence^k * noise3(x / f_k, y / f_k, t[r] / f_k),
+ * f_k = frequency / 2^k, noise3 = OpenSimplex 3-D (2014) with the permutation tables of seeds[r * channels + c]; fp64 arithmetic,
+ * fp32 result, the same slice for every d < depth (depth = 1 for 2-D).  seeds: device int64 [rows * channels], t: device int64
+ * [rows], out: [rows, channels, depth, H, W].  The reference draws its seeds from [-10^10, 10^10); any int64 is accepted.  */
+int ddpm_simplex_noise_f32(float *out, const int64_t *seeds, const int64_t *t, int64_t rows, int channels, int depth, int H, int W,
+                           int octaves, double persistence, double frequency, ddpm_stream_t stream);
 /* torch.optim.Adam.step (no weight decay, no amsgrad) over one flat buffer; step = 1, 2, ...; g is multiplied by grad_scale first
  * (1 / world size after a sum all-reduce).  */
 int ddpm_adam_step_f32(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,

@@ -37,7 +37,7 @@ _FLAGS = [
     ("beta_end", float, 2e-2, "last beta"),
     ("b_scale", float, 1, "data scale applied before noising"),
     ("snr_shift", float, 1, "SNR shift factor of the schedule"),
-    ("simplex_noise", int, 0, "not on this path (must stay 0)"),
+    ("simplex_noise", int, 0, "1: AnoDDPM simplex noise instead of Gaussian (score a model trained with it)"),
     ("batch_size", int, 256, "images per batch"),
     ("augmentation", int, 0, "ignored (as in the reference)"),
     ("cache_data", int, 1, "ignored: data is always cached"),

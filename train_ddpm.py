@@ -27,6 +27,8 @@ def parse_args(argv=None):
         kw = {"default": default}
         if typ not in (None, str):
             kw["type"] = typ
+        if name == "simplex_noise":
+            kw["help"] = "1: train on AnoDDPM simplex noise instead of Gaussian (reconstruct.py must then score with it too)"
         parser.add_argument(f"--{name}", **kw)
     ext = parser.add_argument_group("extensions (defaults: fp32 training)")
     ext.add_argument("--amp", type=int, default=0,
