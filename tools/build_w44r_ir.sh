@@ -6,7 +6,7 @@
 # a0..a127) while the 128 named AGPRs still count in the kernel descriptor (128 + 128 registers, two waves per SIMD).  What does
 # not fit 128 arch VGPRs then spills HONESTLY, to scratch.  tools/asm_spill_report.py prints the spill picture of the result.
 #
-#   tools/build_w44r_ir.sh <out.so> [extra -D flags for conv_wino44r.hip, e.g. -DW44R_SETS=3]
+#   tools/build_w44r_ir.sh <out.so> [extra -D flags for conv_wino44r.hip, e.g. -DW44R_PROBE]
 #
 # Every other translation unit is taken from build/obj (run ddpm_ood_amd/csrc/build.sh first).  VERDICT r5 item 1.
 set -euo pipefail

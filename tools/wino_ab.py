@@ -12,6 +12,16 @@ import torch  # noqa: E402
 from ddpm_ood_amd import ops  # noqa: E402
 
 dev = torch.device("cuda:0")
+# "of peak" as bench.py prices a roofline `frac`: MFMA FLOPs EXECUTED per direct-convolution FLOP / the peak of the pipe that runs them
+F32_MFMA_PEAK_TFLOPS, F16_MFMA_PEAK_TFLOPS = 157.3, 2500.0
+WINO44 = os.environ.get("DDPM_CONV_WINO44", "1") != "0"
+F16X3 = os.environ.get("DDPM_WINO44_F16X3", "1") != "0"
+if WINO44 and F16X3:  # split-f16 F(4x4): four f16 products per fp32 product on 36/144 of the multiplies
+    FORM, EXECUTED, PEAK = "split-f16 F(4x4), f16 MFMA", 4 * 36 / 144, F16_MFMA_PEAK_TFLOPS
+elif WINO44:
+    FORM, EXECUTED, PEAK = "fp32 F(4x4), f32 MFMA", 36 / 144, F32_MFMA_PEAK_TFLOPS
+else:
+    FORM, EXECUTED, PEAK = "fp32 F(2x2), f32 MFMA", 16 / 36, F32_MFMA_PEAK_TFLOPS
 SHAPES = [(256, 128, 0, 128, 32), (256, 256, 128, 128, 32), (256, 256, 0, 256, 16), (256, 256, 256, 256, 16),
           (256, 256, 0, 256, 8), (256, 256, 256, 256, 8)]
 if len(sys.argv) > 1:  # batch size of every shape, e.g. 16 for the small-batch regime
@@ -44,6 +54,6 @@ for B, C1, C2, Cout, H in SHAPES:
     ms = e0.elapsed_time(e1) / n
     tot += ms
     fl = 2.0 * B * H * H * Cout * Cin * 9
-    print(f"{C1}+{C2}->{Cout}@{H}: {ms * 1e3:8.1f} us  {fl / ms / 1e9:7.2f} alg TFLOP/s  ({fl / ms / 1e9 * 16 / 36 / 157.3:.3f} of MFMA peak)  "
+    print(f"{C1}+{C2}->{Cout}@{H}: {ms * 1e3:8.1f} us  {fl / ms / 1e9:7.2f} alg TFLOP/s  ({fl / ms / 1e9 * EXECUTED / PEAK:.3f} of {FORM} peak)  "
           f"err vs direct {err:.1e}", flush=True)
-print(f"REG={os.environ.get('DDPM_W44H_REG', '1')} F16X3={os.environ.get('DDPM_WINO44_F16X3', '1')} WAVES={os.environ.get('DDPM_WINO_WAVES', '8')} WINO44={os.environ.get('DDPM_CONV_WINO44', '1')} SPLIT44={os.environ.get('DDPM_WINO44_SPLIT', '4')} total {tot * 1e3:.1f} us", flush=True)
+print(f"F16X3={os.environ.get('DDPM_WINO44_F16X3', '1')} WAVES={os.environ.get('DDPM_WINO_WAVES', '8')} WINO44={os.environ.get('DDPM_CONV_WINO44', '1')} SPLIT44={os.environ.get('DDPM_WINO44_SPLIT', '4')} total {tot * 1e3:.1f} us", flush=True)
