@@ -9,5 +9,7 @@ from .unet import DiffusionModelUNet  # noqa: F401
 from .scheduler import PNDMScheduler, DDPMScheduler  # noqa: F401
 from .perceptual import PerceptualLoss  # noqa: F401
 from .vqvae import VQVAE, PassthroughVQVAE  # noqa: F401
+from .inferer import DiffusionInferer  # noqa: F401
 
-__all__ = ["DiffusionModelUNet", "PNDMScheduler", "DDPMScheduler", "PerceptualLoss", "VQVAE", "PassthroughVQVAE"]
+__all__ = ["DiffusionModelUNet", "PNDMScheduler", "DDPMScheduler", "PerceptualLoss", "VQVAE", "PassthroughVQVAE",
+           "DiffusionInferer"]

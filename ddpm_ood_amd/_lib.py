@@ -123,6 +123,9 @@ SIGNATURES = {
     "ddpm_plms_step_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int64,
                                      C.c_void_p]),
+    "ddpm_ancestral_step_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_int, C.c_int] + [C.c_float] * 5
+                                + [C.c_uint64, C.c_void_p, C.c_void_p]),
+    "ddpm_randn_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "ddpm_clamp_mse_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "ddpm_vq_nearest_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
     "ddpm_lpips_conv_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 10 + [C.c_void_p]),
@@ -243,7 +246,7 @@ def stream_ptr() -> int:
 
 
 # ---- numeric guard (include/ddpm_ood_hip.h, "Numeric guard of the split-f16 kernel families") -------------------
-STATUS_BITS = {1: "non-finite UNet output (eps) at a PLMS step", 2: "non-finite reconstruction at clamp + MSE",
+STATUS_BITS = {1: "non-finite UNet output (eps) at a PLMS / ancestral step", 2: "non-finite reconstruction at clamp + MSE",
                4: "non-finite latent at the VQ-VAE quantiser", 8: "non-finite gradient after a scaled backward (training)"}
 STATUS_NONFINITE_GRAD = 8
 

@@ -76,6 +76,34 @@ inline bool split_f16_on(bool family) { return family && sw().split_f16; }
 unsigned *status_word();  // device pointer of the current device's word (allocated and zeroed on first use; NULL on failure)
 __device__ __forceinline__ bool non_finite(float v) { return !(__builtin_fabsf(v) <= 3.402823466e+38f); }
 
+// ---- Philox-4x32-10 + Box-Muller: four standard normals per counter ------------------------------------------------------
+// counter = (q, stream), key = seed: a pure function of (seed, stream, q).  ONE generator for ddpm_randn_f32 (training noise,
+// q = element / 4 of the whole tensor) and for the sampling kernels (ddpm_ancestral_step_f32 / ddpm_randn_rows_f32, q = element / 4
+// within a row, stream = the row's own id): a CPU replay fetches the noise of a trajectory through either entry point.
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
+  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1], n3 = (uint32_t)p0;
+  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+  k[0] += 0x9E3779B9u;
+  k[1] += 0xBB67AE85u;
+}
+__device__ __forceinline__ void philox_normal4(int64_t q, uint64_t stream, uint64_t seed, float (&z)[4]) {
+  uint32_t c[4] = {(uint32_t)q, (uint32_t)((uint64_t)q >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
+  uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+#pragma unroll
+  for (int r = 0; r < 10; ++r) philox_round(c, k);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float u1 = ((float)c[2 * h] + 1.0f) * 2.3283064365386963e-10f;  // (0, 1]
+    const float u2 = (float)c[2 * h + 1] * 2.3283064365386963e-10f;
+    const float rad = sqrtf(-2.0f * logf(u1 < 1e-30f ? 1e-30f : u1));
+    float sn, cs;
+    sincosf(6.283185307179586f * u2, &sn, &cs);
+    z[2 * h] = rad * cs;
+    z[2 * h + 1] = rad * sn;
+  }
+}
+
 // ---- in-situ profiler (api.hip) ----------------------------------------------------------------
 extern bool g_prof_on;
 void prof_begin(hipStream_t s, const char *kernel, double flops, double bytes);

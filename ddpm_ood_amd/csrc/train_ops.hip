@@ -618,31 +618,12 @@ __global__ void fill_kernel(float *__restrict__ out, float value, int64_t n) {
 // Standard normals from Philox-4x32-10 (counter = (element / 4, stream), key = seed) + Box-Muller: four values per counter, a
 // pure function of (seed, stream, element index) -- the training noise does not have to reproduce torch's generator, it has to
 // be reproducible and independent across ranks / steps (stream = step counter, seed mixes in the rank).
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1], n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-  k[0] += 0x9E3779B9u;
-  k[1] += 0xBB67AE85u;
-}
+// (philox_normal4 lives in common.h: the sampling kernels of sampling.hip add the very same normals)
 __global__ void randn_kernel(float *__restrict__ out, int64_t n, uint64_t seed, uint64_t stream) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // four outputs per thread
   if (4 * q >= n) return;
-  uint32_t c[4] = {(uint32_t)q, (uint32_t)((uint64_t)q >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
-  uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) philox_round(c, k);
   float z[4];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float u1 = ((float)c[2 * h] + 1.0f) * 2.3283064365386963e-10f;  // (0, 1]
-    const float u2 = (float)c[2 * h + 1] * 2.3283064365386963e-10f;
-    const float rad = sqrtf(-2.0f * logf(u1 < 1e-30f ? 1e-30f : u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z[2 * h] = rad * cs;
-    z[2 * h + 1] = rad * sn;
-  }
+  philox_normal4(q, stream, seed, z);
 #pragma unroll
   for (int j = 0; j < 4; ++j)
     if (4 * q + j < n) out[4 * q + j] = z[j];

@@ -288,6 +288,29 @@ def read_png(path: str) -> np.ndarray:
     return a[..., 0] if channels == 1 else a
 
 
+def write_png(path, image: np.ndarray) -> None:
+    """The inverse of ``read_png`` for what sample grids need: uint8 [H, W] (greyscale) or [H, W, 3] (RGB), 8 bits, filter 0 on
+    every scanline, one IDAT chunk; zlib only."""
+    import struct
+    import zlib
+
+    a = np.ascontiguousarray(image)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)) or a.size == 0:
+        raise ValueError(f"write_png: expected uint8 [H, W] or [H, W, 3], got {a.dtype} {a.shape}")
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[..., 0]
+    h, w = a.shape[:2]
+    rows = a.reshape(h, -1)
+    raw = np.concatenate([np.zeros((h, 1), dtype=np.uint8), rows], axis=1).tobytes()  # filter type 0 before every scanline
+
+    def chunk(kind: bytes, body: bytes) -> bytes:
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, 0 if a.ndim == 2 else 2, 0, 0, 0)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
 def read_pnm(path: str) -> np.ndarray:
     """Binary PGM (P5) / PPM (P6) -> [H, W] or [H, W, 3] float32."""
     data = open(path, "rb").read()

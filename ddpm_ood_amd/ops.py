@@ -626,6 +626,68 @@ def plms_step(sample, ets, kind: int, sample_coeff: float, coef_eps: float, deno
     return out
 
 
+PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1, "sample": 2}  # DDPM_PREDICTION_* of the header
+_U64 = (1 << 64) - 1
+
+
+def row_streams_tensor(row_streams, device) -> torch.Tensor:
+    """Philox stream ids of the rows as the device array the sampling kernels read: uint64 values carried in an int64 tensor
+    (the same bits)."""
+    if isinstance(row_streams, torch.Tensor):
+        if row_streams.dtype != torch.int64 or not row_streams.is_cuda:
+            raise TypeError("row_streams must be an int64 ROCm device tensor (or a sequence of ints)")
+        return row_streams.contiguous()
+    vals = [int(s) & _U64 for s in row_streams]
+    return torch.tensor([v - (1 << 64) if v >> 63 else v for v in vals], dtype=torch.int64, device=device)
+
+
+def randn_rows(shape, seed: int, row_streams, device=None):
+    """[B, ...] standard normals, row b a pure function of (seed, row_streams[b]): Philox counter j / 4 within the row.  Exactly
+    the noise ``ancestral_step`` adds for the same (seed, row_streams); a single row with stream s equals
+    ``train_ops.randn`` of the same length for (seed, s)."""
+    lib = _lib.load()
+    if device is None:
+        if not isinstance(row_streams, torch.Tensor):
+            raise ValueError("randn_rows: device is required when row_streams is not a device tensor")
+        device = row_streams.device
+    streams = row_streams_tensor(row_streams, device)
+    shape = tuple(int(s) for s in shape)
+    if not shape or streams.shape != (shape[0],):
+        raise ValueError(f"randn_rows: {tuple(streams.shape)} stream ids for shape {shape}")
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    check(lib.ddpm_randn_rows_f32(ptr(out), shape[0], out[0].numel(), int(seed) & _U64, ptr(streams), stream_ptr()), "randn_rows")
+    return out
+
+
+def ancestral_step(sample, model_output, *, sqrt_ac: float, sqrt_1m_ac: float, c0: float, ct: float, sigma: float, seed: int = 0,
+                   row_streams=None, prediction_type: str = "epsilon", clip_sample: bool = True, return_pred: bool = True,
+                   out=None):
+    """One fused DDPM reverse step (ddpm_ancestral_step_f32): returns (prev_sample, pred_original_sample or None).
+    ``row_streams`` may be None only when sigma == 0 (no noise is drawn then)."""
+    lib = _lib.load()
+    sample = require_device_f32(sample, "sample")
+    model_output = require_device_f32(model_output, "model_output")
+    if model_output.shape != sample.shape:
+        raise ValueError(f"model_output {tuple(model_output.shape)} does not match sample {tuple(sample.shape)}")
+    if prediction_type not in PREDICTION_TYPES:
+        raise ValueError(f"unknown prediction_type {prediction_type}")
+    B = sample.shape[0]
+    streams = None
+    if float(sigma) != 0.0:
+        if row_streams is None:
+            raise ValueError("ancestral_step: row_streams is required when sigma != 0")
+        streams = row_streams_tensor(row_streams, sample.device)
+        if streams.shape != (B,):
+            raise ValueError(f"ancestral_step: {tuple(streams.shape)} stream ids for a batch of {B}")
+    if out is None:
+        out = torch.empty_like(sample)
+    pred = torch.empty_like(sample) if return_pred else None
+    check(lib.ddpm_ancestral_step_f32(ptr(sample), ptr(model_output), ptr(out), ptr(pred), B, sample[0].numel(),
+                                      PREDICTION_TYPES[prediction_type], int(bool(clip_sample)), sqrt_ac, sqrt_1m_ac, c0, ct,
+                                      sigma, int(seed) & _U64, ptr(streams), stream_ptr()), "ancestral_step")
+    return out, pred
+
+
 def clamp_mse_(orig, recon, b_scale: float = 1.0):
     """In place: recon <- clamp(recon / b_scale, 0, 1); returns per-image MSE [B]."""
     lib = _lib.load()

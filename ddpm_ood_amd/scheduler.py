@@ -11,6 +11,8 @@ host as fp32 torch CPU scalars (bit-identical to what the reference computes wit
 tensors); device side: ONE fused kernel per step (ddpm_plms_step_f32) instead of 2-6
 full-tensor ATen launches, and one for add_noise.  PLMS state (ets, counter, cur_sample)
 persists across calls until set_timesteps, exactly like the reference (quirk Q3).
+``DDPMScheduler.set_timesteps`` / ``.step`` are the ancestral sampler of the same package (one fused kernel per step as well,
+noise drawn inside it); the reference reaches it through ``DiffusionInferer.sample`` in its validation epoch.
 """
 
 from __future__ import annotations
@@ -66,11 +68,133 @@ class Scheduler:
         return ops.add_noise(original_samples, noise, sa, sb, b_scale)
 
 
+SAMPLING_KEY_TAG = 1 << 63
+STREAMS_PER_ROW = 65536
+
+
+def sampling_key(seed: int) -> int:
+    """Philox key of the sampling noise: bit 63 set over the low 63 bits of ``seed``.  The training step keys its noise with
+    ``seed * 7919 + rank`` (train.py), which stays below 2^63 for every seed below 1.1e15, so no (key, stream) pair of a sampling
+    run can coincide with one of a training run, whatever the two seeds are."""
+    return SAMPLING_KEY_TAG | (int(seed) & (SAMPLING_KEY_TAG - 1))
+
+
+def sampling_streams(row_ids, timestep: int):
+    """Philox stream id of row b at step t: ``row_ids[b] * 65536 + t`` (x_T: t = num_train_timesteps).  A row's noise depends on
+    its own id and the step only -- not on the batch it rides in, its position in it, or the rank that draws it."""
+    t = int(timestep)
+    if not 0 <= t < STREAMS_PER_ROW:
+        raise ValueError(f"timestep {t} outside [0, {STREAMS_PER_ROW})")
+    return [int(r) * STREAMS_PER_ROW + t for r in row_ids]
+
+
 class DDPMScheduler(Scheduler):
-    def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta",
-                 prediction_type: str = "epsilon", **schedule_args):
+    """``generative.networks.schedulers.DDPMScheduler``: constructor, ``add_noise``, ``set_timesteps`` and the ancestral
+    ``step`` (Ho et al. 2020, eq. 7 and algorithm 2), the latter as ONE fused launch (ops.ancestral_step) with the noise drawn
+    inside the kernel.
+
+    Quirk Q22 (kept, it is the package's behaviour): ``step`` takes abar_{t-1} from ``alphas_cumprod[t - 1]`` (1 at t = 0)
+    WHATEVER ``set_timesteps`` chose -- with 25 inference steps the update at t = 960 still uses abar_959, not abar_920, so a
+    shortened schedule is not the DDPM posterior of the strided chain.
+    """
+
+    def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", variance_type: str = "fixed_small",
+                 clip_sample: bool = True, prediction_type: str = "epsilon", **schedule_args):
         super().__init__(num_train_timesteps, schedule, **schedule_args)
+        if variance_type in ("learned", "learned_range"):
+            raise NotImplementedError(f"variance_type {variance_type}: learned variances are not built (the UNets here "
+                                      f"predict one tensor)")
+        if variance_type not in ("fixed_small", "fixed_large"):
+            raise ValueError("Argument `variance_type` must be a member of `DDPMVarianceType`")
+        if prediction_type not in ops.PREDICTION_TYPES:
+            raise ValueError("Argument `prediction_type` must be a member of `DDPMPredictionType`")
         self.prediction_type = prediction_type
+        self.variance_type = variance_type
+        self.clip_sample = bool(clip_sample)
+        self.num_inference_steps = None
+        self._coef_cache = {}
+        self._coef_tables = (None, None, None)
+        self._stream_table = None  # (row ids, device, int64 [T + 1, B] device tensor of stream ids)
+
+    def set_timesteps(self, num_inference_steps: int, device=None) -> None:
+        if num_inference_steps > self.num_train_timesteps:
+            raise ValueError(
+                f"`num_inference_steps`: {num_inference_steps} cannot be larger than `self.num_train_timesteps`:"
+                f" {self.num_train_timesteps}")
+        self.num_inference_steps = num_inference_steps
+        step_ratio = self.num_train_timesteps // self.num_inference_steps
+        ts = (np.arange(0, num_inference_steps) * step_ratio).round()[::-1].astype(np.int64)
+        self.timesteps = torch.from_numpy(ts.copy())  # host tensor, as PNDMScheduler's
+
+    def step_coefficients(self, timestep: int):
+        """(sqrt(abar_t), sqrt(1 - abar_t), c0, ct, sigma) of one reverse step, evaluated in float64 from the tables as they are
+        AT CALL TIME (snr_shift_tables reassigns them) and memoised per (t, table):
+          c0 = sqrt(abar_{t-1}) beta_t / (1 - abar_t),  ct = sqrt(alpha_t) (1 - abar_{t-1}) / (1 - abar_t),
+          sigma^2 = (1 - abar_{t-1}) / (1 - abar_t) beta_t floored at 1e-20 (fixed_small) or beta_t (fixed_large); sigma = 0 at
+          t = 0 (the last step adds no noise).  abar_{t-1} = alphas_cumprod[t - 1], 1 at t = 0 (quirk Q22)."""
+        t = int(timestep)
+        tables = (self.alphas_cumprod, self.betas, self.alphas)
+        if not all(a is b for a, b in zip(tables, self._coef_tables)):
+            # the tables were reassigned: drop what was computed from the old ones, and hold the new ones so that no id() in a
+            # live key can be reused by a later tensor
+            self._coef_cache.clear()
+            self._coef_tables = tables
+        key = (t, id(self.alphas_cumprod), id(self.betas), id(self.alphas), self.variance_type)
+        hit = self._coef_cache.get(key)
+        if hit is not None:
+            return hit
+        if not 0 <= t < self.num_train_timesteps:
+            raise ValueError(f"timestep {t} outside [0, {self.num_train_timesteps})")
+        a_t = float(self.alphas_cumprod[t])
+        a_p = float(self.alphas_cumprod[t - 1]) if t > 0 else 1.0
+        beta, alpha = float(self.betas[t]), float(self.alphas[t])
+        c0 = a_p ** 0.5 * beta / (1.0 - a_t)
+        ct = alpha ** 0.5 * (1.0 - a_p) / (1.0 - a_t)
+        if t == 0:
+            sigma = 0.0
+        elif self.variance_type == "fixed_small":
+            sigma = max((1.0 - a_p) / (1.0 - a_t) * beta, 1e-20) ** 0.5
+        else:
+            sigma = beta ** 0.5
+        out = (a_t ** 0.5, (1.0 - a_t) ** 0.5, c0, ct, sigma)
+        self._coef_cache[key] = out
+        return out
+
+    def _streams(self, row_ids, timestep: int, device) -> torch.Tensor:
+        """The [B] device array of stream ids of this step: a row of a [T + 1, B] table uploaded once per (row ids, device),
+        so that a step launches nothing besides its kernel."""
+        ids = tuple(int(r) for r in row_ids)
+        tab = self._stream_table
+        if tab is None or tab[0] != ids or tab[1] != device:
+            T = self.num_train_timesteps
+            if any(r < 0 or r >= (1 << 47) for r in ids) or T >= STREAMS_PER_ROW:
+                raise ValueError("row ids must lie in [0, 2^47) and num_train_timesteps below 65536")
+            host = (torch.tensor(ids, dtype=torch.int64)[None, :] * STREAMS_PER_ROW
+                    + torch.arange(T + 1, dtype=torch.int64)[:, None])
+            tab = (ids, device, host.to(device))
+            self._stream_table = tab
+        return tab[2][int(timestep)]
+
+    def initial_noise(self, shape, *, seed: int = 0, row_ids=None, device=None) -> torch.Tensor:
+        """x_T: row b = the normals of stream ``row_ids[b] * 65536 + num_train_timesteps`` under ``sampling_key(seed)``."""
+        ids = range(int(shape[0])) if row_ids is None else row_ids
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return ops.randn_rows(shape, sampling_key(seed), self._streams(ids, self.num_train_timesteps, device))
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, *, seed: int = 0, row_ids=None):
+        """x_{t-1} ~ p(x_{t-1} | x_t): returns (prev_sample, pred_original_sample).
+
+        The noise of row b is drawn in the kernel from Philox stream ``row_ids[b] * 65536 + t`` (``row_ids`` defaults to
+        0 .. B - 1) under the key ``sampling_key(seed)`` = 2^63 | seed: disjoint from the training step's keys
+        ``seed * 7919 + rank`` < 2^63, so sampling never replays training noise.  ``ops.randn_rows`` with the same key and
+        stream ids returns exactly the z this call adds."""
+        t = int(timestep)
+        sa, sb, c0, ct, sigma = self.step_coefficients(t)
+        ids = range(sample.shape[0]) if row_ids is None else row_ids
+        streams = self._streams(ids, t, sample.device) if sigma != 0.0 else None
+        return ops.ancestral_step(sample, model_output, sqrt_ac=sa, sqrt_1m_ac=sb, c0=c0, ct=ct, sigma=sigma,
+                                  seed=sampling_key(seed), row_streams=streams, prediction_type=self.prediction_type,
+                                  clip_sample=self.clip_sample)
 
 
 class PNDMScheduler(Scheduler):
@@ -92,6 +216,7 @@ class PNDMScheduler(Scheduler):
         self.steps_offset = steps_offset
         self.timestep_list = timestep_list  # 100-entry (default) vs 101-entry list
         self._coef_cache = {}
+        self._coef_table = None
         self.cur_model_output = 0
         self.counter = 0
         self.cur_sample = None
@@ -116,6 +241,10 @@ class PNDMScheduler(Scheduler):
         # one timestep, it does not change the ratio (diffusers keeps the requested count for it)
         self._step_ratio = step_ratio
         self.num_inference_steps = len(self.timesteps)
+        self.reset()
+
+    def reset(self) -> None:
+        """Forget the PLMS history (it belongs to one trajectory); the timestep list stays as set_timesteps left it."""
         self.ets = []
         self.counter = 0
         self.cur_sample = None
@@ -126,6 +255,9 @@ class PNDMScheduler(Scheduler):
     def plms_coefficients(self, timestep: int, prev_timestep: int):
         """fp32 scalars of _get_prev_sample, computed with the same 0-d torch CPU ops as the reference (memoised per
         (timestep, prev_timestep, table): ~70 us of 0-d tensor arithmetic otherwise, on every PLMS step)."""
+        if self.alphas_cumprod is not self._coef_table:  # reassigned (snr_shift_tables): the old entries are stale, and the
+            self._coef_cache.clear()                     # held table keeps its id() from being reused
+            self._coef_table = self.alphas_cumprod
         key = (timestep, prev_timestep, id(self.alphas_cumprod))
         hit = self._coef_cache.get(key)
         if hit is not None:

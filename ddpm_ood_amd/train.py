@@ -24,7 +24,8 @@ dict of base.py:166-187.  Differences, on purpose:
     onto `noise` also under v_prediction); --augmentation / --cache_data / --num_workers are accepted and have no effect
     (the reference's two augmentation branches are identical, get_train_and_val_dataloader.py:87-91; the images are
     resident tensors here);
-  * no TensorBoard / matplotlib sample grids (not installed here; off the path).
+  * no TensorBoard; the validation sample grid (ddpm_trainer.py:177-216) is opt-in (``DDPM_VAL_SAMPLES=1``: 1000 more forwards
+    per validation epoch) and is written as .npy / .png files under <run_dir>/val instead of a matplotlib figure.
 """
 
 from __future__ import annotations
@@ -289,8 +290,41 @@ class DDPMTrainer(BaseTrainer):
             n += batch["image"].shape[0]
             if self.quick_test:
                 break
+        if self.native:
+            self.stepper._tape = None  # a validation forward is never followed by a backward: free its activations
         print(f"Validation {epoch}: loss {tot / max(n, 1):.6f}")
+        if n and os.environ.get("DDPM_VAL_SAMPLES", "0") in ("1", "on"):
+            self._val_samples(epoch, img)
         return tot / max(n, 1)
+
+    @torch.no_grad()
+    def _val_samples(self, epoch: int, last_images: torch.Tensor) -> None:
+        """The reference's sample grid (ddpm_trainer.py:177-216), opt-in through DDPM_VAL_SAMPLES=1: 8 samples (4 from 128
+        pixels up, 2 for 3-D) of the last validation batch's latent shape through the 1000-step ancestral sampler, inverse latent
+        pad, stage-1 decode -> <run_dir>/val/samples_epoch{E}.npy / .png, written by rank 0.  The forwards are the INFERENCE
+        engine's (``self.model(...)``: no tape); ``adam_step`` marks the engine's packed weights stale after every update, so the
+        first forward here re-packs them (and drops captured graphs) from the parameters as they are now."""
+        if self.rank != 0:
+            return
+        from .inferer import DiffusionInferer
+        from .sampling import decode_latents, draw_latents, make_sampling_scheduler, write_samples
+
+        lat = self.vqvae_model.encode_stage_2_inputs(last_images[:1]).float()
+        if self.do_latent_pad:
+            lat = F.pad(input=lat, pad=self.latent_pad, mode="constant", value=0)
+        if self.spatial_dimension == 3:
+            num = 2
+        else:
+            num = 4 if lat.shape[2] >= 128 else 8
+        sched = make_sampling_scheduler("ddpm", prediction_type=self.prediction_type, beta_schedule=self.beta_schedule,
+                                        beta_start=self.beta_start, beta_end=self.beta_end, snr_shift=self.snr_shift)
+        t0 = time.time()
+        latents = draw_latents(self.model, sched, DiffusionInferer(), range(num), tuple(lat.shape[1:]),
+                               self.seed * 1_000_003 + epoch, self.device)
+        samples = decode_latents(latents, self.vqvae_model, self.inverse_latent_pad if self.do_latent_pad else None,
+                                 self.b_scale)
+        write_samples(self.run_dir / "val", f"samples_epoch{epoch}", samples.cpu().numpy())
+        print(f"Validation {epoch}: {num} samples in {time.time() - t0:.1f} s -> {self.run_dir / 'val'}")
 
     def save_checkpoint(self, path, epoch, save_message=None):
         if self.rank != 0:

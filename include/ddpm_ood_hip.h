@@ -305,6 +305,29 @@ int ddpm_plms_step_f32(const float *sample, const float *e0, const float *e1, co
                        int kind, int v_prediction, float v_a, float v_b, float sample_coeff, float coef_eps,
                        float denom, float *prev, int64_t numel, ddpm_stream_t stream);
 
+/* DDPMScheduler.step: one ancestral reverse step x_t -> x_{t-1} of a [B, row_numel] batch in ONE launch (sampling.hip).
+ *   x0   = (sample - sqrt_1m_ac * out) / sqrt_ac    DDPM_PREDICTION_EPSILON
+ *        = sqrt_ac * sample - sqrt_1m_ac * out      DDPM_PREDICTION_V
+ *        = out                                      DDPM_PREDICTION_SAMPLE
+ *   x0   = clamp(x0, -1, 1) if clip_sample;  mean = c0 * x0 + ct * sample;  prev = mean + sigma * z
+ * z is generated in the kernel: element j of row b is value j % 4 of Philox-4x32-10 counter (j / 4, row_streams[b]) under key
+ * `seed`, through the Box-Muller arithmetic of the training noise generator below -- a row is a function of (seed, its stream
+ * id) alone.  sigma == 0 (the last step): no noise is drawn and row_streams may be NULL.  row_streams: DEVICE array [B].
+ * pred_original: NULL, or receives x0.  prev may alias sample.  A non-finite model output sets DDPM_STATUS_NONFINITE_EPS.
+ * 16-byte accesses when row_numel % 4 == 0 and every pointer is 16-byte aligned, a scalar path otherwise.               */
+#define DDPM_PREDICTION_EPSILON 0
+#define DDPM_PREDICTION_V 1
+#define DDPM_PREDICTION_SAMPLE 2
+int ddpm_ancestral_step_f32(const float *sample, const float *model_output, float *prev, float *pred_original, int B,
+                            int64_t row_numel, int prediction_type, int clip_sample, float sqrt_ac, float sqrt_1m_ac,
+                            float c0, float ct, float sigma, uint64_t seed, const uint64_t *row_streams,
+                            ddpm_stream_t stream);
+/* out[b, j] = exactly the z the call above adds for (seed, row_streams[b]): draws x_T, and lets a test or a CPU replay see the
+ * noise a trajectory used.  A single row with stream id s holds the values the training generator writes for
+ * (seed, s) over the same length.                                                                                            */
+int ddpm_randn_rows_f32(float *out, int B, int64_t row_numel, uint64_t seed, const uint64_t *row_streams,
+                        ddpm_stream_t stream);
+
 /* recon = clamp(recon * inv_b_scale... (recon / b_scale), 0, 1) in place and
  * mse[b] = mean((orig - recon)^2) (src/trainers/reconstruct.py:167-168,188-191).          */
 int ddpm_clamp_mse_f32(const float *orig, float *recon, float b_scale, float *mse, int B, int64_t chw,
@@ -441,7 +464,7 @@ int ddpm_attention_ws_f32(const float *qkv, const float *residual, float *out, i
  * while the split-f16 kernels are on, run the batch again after ddpm_set_split_f16(0); a word that is still set then is
  * a genuine fp32 overflow and the NaN is written like the reference would.
  * ---------------------------------------------------------------------------------- */
-#define DDPM_STATUS_NONFINITE_EPS 1u    /* ddpm_plms_step_f32 read a non-finite model output           */
+#define DDPM_STATUS_NONFINITE_EPS 1u    /* ddpm_plms_step_f32 / ddpm_ancestral_step_f32 read a non-finite model output */
 #define DDPM_STATUS_NONFINITE_RECON 2u  /* ddpm_clamp_mse_f32 read a non-finite reconstruction          */
 #define DDPM_STATUS_NONFINITE_LATENT 4u /* ddpm_vq_nearest_f32 read a non-finite latent                 */
 #define DDPM_STATUS_NONFINITE_GRAD 8u   /* ddpm_scale_check_f32 read a non-finite gradient (training)   */
