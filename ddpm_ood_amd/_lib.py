@@ -128,6 +128,10 @@ SIGNATURES = {
     "ddpm_randn_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "ddpm_clamp_mse_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "ddpm_vq_nearest_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    "ddpm_vq_train_partials": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
+    "ddpm_vq_train_assign_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_void_p]),
+    "ddpm_vq_train_update_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "ddpm_vq_train_backward_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p]),
     "ddpm_lpips_conv_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 10 + [C.c_void_p]),
     "ddpm_maxpool3s2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "ddpm_lpips_conv_biasmap_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p]),

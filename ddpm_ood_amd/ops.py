@@ -808,6 +808,73 @@ def vq_nearest(x, codebook):
     return idx.long(), out
 
 
+def _vq_shapes(x, e):
+    B, D = x.shape[:2]
+    K = e.shape[0]
+    if e.ndim != 2 or e.shape[1] != D:
+        raise ValueError(f"codebook is {tuple(e.shape)} but the latent has {D} channels")
+    return B, D, x[0, 0].numel(), K
+
+
+def vq_train_assign(x, codebook, commitment_cost: float = 0.25):
+    """VQ-VAE quantiser, training path (vq.hip): the search of ``vq_nearest`` plus what the EMA update and the loss need.
+    -> (idx int32 [B, *spatial], out = x + (codebook[idx] - x), counts [K], dw [K, D], loss 0-dim, sums [K (D + 1)]).
+    counts / dw are views of ``sums`` (one allocation: ONE all_reduce over ranks before ``vq_train_update``); loss =
+    commitment_cost * mean((codebook[idx] - x)^2).  counts, dw and loss are bit-identical run to run."""
+    lib = _lib.load()
+    x = require_device_f32(x, "x")
+    e = require_device_f32(codebook, "codebook")
+    B, D, S, K = _vq_shapes(x, e)
+    idx = torch.empty((B,) + tuple(x.shape[2:]), dtype=torch.int32, device=x.device)
+    out = torch.empty_like(x)
+    norms = torch.empty(K, dtype=torch.float32, device=x.device)
+    sums = torch.empty(K * (D + 1), dtype=torch.float32, device=x.device)
+    counts, dw = sums[:K], sums[K:].view(K, D)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    partials = torch.empty(max(1, lib.ddpm_vq_train_partials(B, D, S)), dtype=torch.float64, device=x.device)
+    check(lib.ddpm_vq_train_assign_f32(ptr(x), ptr(e), ptr(norms), idx.data_ptr(), ptr(out), ptr(counts), ptr(dw), ptr(loss),
+                                       partials.data_ptr(), B, D, S, K, float(commitment_cost), stream_ptr()), "vq_train_assign")
+    return idx, out, counts, dw, loss, sums
+
+
+def _inplace_f32(t, name, shape):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
+            tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a contiguous float32 ROCm tensor of shape {tuple(shape)} (it is updated in place)")
+    return t
+
+
+def vq_train_update(ema_cluster_size, ema_w, codebook, counts, dw, decay: float, epsilon: float) -> None:
+    """EMA codebook update, one launch, in place on the three state tensors (formulas: include/ddpm_ood_hip.h)."""
+    lib = _lib.load()
+    K, D = codebook.shape
+    _inplace_f32(ema_cluster_size, "ema_cluster_size", (K,))
+    _inplace_f32(ema_w, "ema_w", (K, D))
+    _inplace_f32(codebook, "codebook", (K, D))
+    counts, dw = require_device_f32(counts, "counts"), require_device_f32(dw, "dw")
+    if counts.numel() != K or dw.numel() != K * D:
+        raise ValueError(f"counts / dw are {tuple(counts.shape)} / {tuple(dw.shape)} for a [{K}, {D}] codebook")
+    check(lib.ddpm_vq_train_update_f32(ptr(ema_cluster_size), ptr(ema_w), ptr(codebook), ptr(counts), ptr(dw), K, D, float(decay),
+                                       float(epsilon), stream_ptr()), "vq_train_update")
+
+
+def vq_train_backward(dout, x, codebook, idx, dloss, commitment_cost: float = 0.25):
+    """dx = dout + (2 commitment_cost / numel) (x - codebook[idx]) dloss; ``codebook`` is the one ``vq_train_assign`` searched.
+    dout / dloss may be None (that term is zero)."""
+    lib = _lib.load()
+    x = require_device_f32(x, "x")
+    e = require_device_f32(codebook, "codebook")
+    B, D, S, K = _vq_shapes(x, e)
+    if idx.dtype != torch.int32 or not idx.is_cuda or idx.numel() != B * S:
+        raise ValueError("idx must be the int32 device tensor vq_train_assign returned")
+    dout = None if dout is None else require_device_f32(dout, "dout")
+    dloss = None if dloss is None else require_device_f32(dloss, "dloss")
+    dx = torch.empty_like(x)
+    check(lib.ddpm_vq_train_backward_f32(ptr(dout), ptr(x), ptr(e), idx.contiguous().data_ptr(), ptr(dloss), ptr(dx), B, D, S,
+                                         float(commitment_cost), stream_ptr()), "vq_train_backward")
+    return dx
+
+
 # ---- simplex noise (src/utils/simplex_noise.py: generate_simplex_noise) ----------------------------------
 
 def simplex_noise(shape, seeds, t, octaves: int = 6, persistence: float = 0.8, frequency: float = 64.0, device=None):

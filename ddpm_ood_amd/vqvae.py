@@ -218,8 +218,11 @@ class _Stack(nn.Module):
 
 
 class _EMAQuantizer(nn.Module):
-    def __init__(self, num_embeddings, embedding_dim):
+    def __init__(self, num_embeddings, embedding_dim, commitment_cost=0.25, decay=0.99, epsilon=1e-5, ddp_sync=True):
         super().__init__()
+        # hyper-parameters of the training step (vqvae_train.py reads them; nothing on the eval path does)
+        self.num_embeddings, self.embedding_dim = num_embeddings, embedding_dim
+        self.commitment_cost, self.decay, self.epsilon, self.ddp_sync = commitment_cost, decay, epsilon, ddp_sync
         self.embedding = nn.Embedding(num_embeddings, embedding_dim)
         self.register_buffer("ema_cluster_size", torch.zeros(num_embeddings))
         self.register_buffer("ema_w", self.embedding.weight.data.clone())
@@ -238,6 +241,7 @@ class _VectorQuantizer(nn.Module):
     def __init__(self, quantizer):
         super().__init__()
         self.quantizer = quantizer
+        self.perplexity = torch.zeros(1)  # set by vqvae_train.vqvae_forward_train (no RNG draw here: construction order is pinned by tests)
 
     def forward(self, x):
         return self.quantizer(x)
@@ -246,8 +250,8 @@ class _VectorQuantizer(nn.Module):
 class VQVAE(nn.Module):
     """MONAI-Generative's VQVAE as the reconstruction path uses it (reference: /root/reference/src/trainers/base.py:44-61,
     /root/reference/src/trainers/reconstruct.py:124,166): inference only, on the device only -- every layer runs on a HIP kernel
-    of libddpm_ood_hip (CPU tensors raise; parameters are read detached, so nothing here is differentiable: VQ-VAE TRAINING is
-    off the path).  3-D README shapes take the MFMA kernels; 2-D stride-1 3x3 layers with Cout % 128 == 0 and
+    of libddpm_ood_hip (CPU tensors raise; parameters are read detached, so nothing here is differentiable: TRAINING goes through
+    ``vqvae_train.vqvae_forward_train``, which evaluates these same parameter holders, never through ``forward`` or ``self.training``).  3-D README shapes take the MFMA kernels; 2-D stride-1 3x3 layers with Cout % 128 == 0 and
     Cin % 4 == 0 the UNet's MFMA convolution (Winograd forms only for the conv_only layers: they have no output activation); everything else the generic kernel ddpm_convnd_generic_f32 (correct,
     slow: one thread per output), announced once per layer shape on stderr."""
 
@@ -268,6 +272,7 @@ class VQVAE(nn.Module):
             raise NotImplementedError("only act='RELU' / output_act=None (the reference's configuration)")
         self.spatial_dims, self.in_channels, self.out_channels = spatial_dims, in_channels, out_channels
         self.num_embeddings, self.embedding_dim = num_embeddings, embedding_dim
+        self.dropout = dropout  # (only vqvae_train looks at it: a non-zero value is not built)
         sd, n = spatial_dims, len(num_channels)
         enc = []
         for i in range(n):
@@ -284,7 +289,8 @@ class VQVAE(nn.Module):
             dec.append(_Convolution(sd, rc[i], out_channels if i == n - 1 else rc[i + 1], s, k, dil, pad, opad,
                                     conv_only=i == n - 1, is_transposed=True))
         self.decoder = _Stack(dec)
-        self.quantizer = _VectorQuantizer(_EMAQuantizer(num_embeddings, embedding_dim))
+        self.quantizer = _VectorQuantizer(_EMAQuantizer(num_embeddings, embedding_dim, commitment_cost, decay, epsilon,
+                                                         ddp_sync))
 
     def encode(self, images):
         return self.encoder(images)

@@ -341,6 +341,26 @@ int ddpm_clamp_mse_f32(const float *orig, float *recon, float b_scale, float *ms
 int ddpm_vq_nearest_f32(const float *x, const float *codebook, float *code_norms, int *idx, float *out, int B, int D,
                         int64_t S, int K, ddpm_stream_t stream);
 
+/* Training step of the EMA quantiser (MONAI-Generative's EMAQuantizer in training mode; src/trainers/vqvae_trainer.py reaches
+ * it through the VQ-VAE's forward).  Entry points added without an ABI bump.
+ * assign: the search of ddpm_vq_nearest_f32 (idx and out are bit-identical to its), and
+ *   counts[k] = #{p: idx[p] = k} (exact), dw[k, :] = sum of x[p, :] over those p in ascending p (fp32 recursive summation in a
+ *   fixed order: bit-identical run to run, no float atomics), loss[0] = commitment_cost * mean((e_idx - x)^2) over B D S
+ *   elements (fp64 accumulation, fixed order).  partials: ddpm_vq_train_partials(B, D, S) doubles of scratch.  counts and dw
+ *   may be adjacent in one allocation (one all_reduce over ranks between assign and update).
+ * update, in place, one launch: cs <- decay cs + (1 - decay) counts; n = sum_k cs; w_k = (cs_k + epsilon) / (n + K epsilon) n;
+ *   ema_w <- decay ema_w + (1 - decay) dw; codebook_k <- ema_w_k / w_k.  fp64 arithmetic between fp32 loads and stores.
+ * backward: dx = dout + (2 commitment_cost / (B D S)) (x - e_idx) dloss[0]; dout or dloss may be NULL (that term is 0);
+ *   codebook is the one assign searched (before update).                                                                      */
+size_t ddpm_vq_train_partials(int B, int D, int64_t S);
+int ddpm_vq_train_assign_f32(const float *x, const float *codebook, float *code_norms, int *idx, float *out, float *counts,
+                             float *dw, float *loss, double *partials, int B, int D, int64_t S, int K, float commitment_cost,
+                             ddpm_stream_t stream);
+int ddpm_vq_train_update_f32(float *ema_cluster_size, float *ema_w, float *codebook, const float *counts, const float *dw,
+                             int K, int D, float decay, float epsilon, ddpm_stream_t stream);
+int ddpm_vq_train_backward_f32(const float *dout, const float *x, const float *codebook, const int *idx, const float *dloss,
+                               float *dx, int B, int D, int64_t S, float commitment_cost, ddpm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * LPIPS-AlexNet (PerceptualLoss.forward, src/losses/perceptual_loss.py:105-186; call site
  * src/trainers/reconstruct.py:172-187).  The three 3x3 layers of AlexNet go through

@@ -1,0 +1,138 @@
+"""Time the HIP quantiser training step (assign + update + backward) against the same arithmetic in torch ops on the same
+device (one-hot, mm, EMA lines, mse_loss) -- same process, same box, medians of event-timed repetitions.  Results:
+profiles/vqvae_training.md.
+
+    python tools/vqvae_train_bench.py [--reps 50] [--full-step 1]
+    rocprofv3 --kernel-trace --stats -d out -o step -- python tools/vqvae_train_bench.py --quantiser 0 --reps 25
+"""
+import argparse
+import statistics
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+
+def timed(fn, reps, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3)
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def quantiser(N, D, K, reps, dev):
+    from ddpm_ood_amd import ops
+
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(N // 512, D, 8, 8, 8, generator=g).to(dev)  # volumes of 8^3 latent positions
+    E0 = torch.randn(K, D, generator=g).to(dev)
+    dout, dloss = torch.randn(x.shape, generator=g).to(dev), torch.ones((), device=dev)
+    cc, decay, eps = 0.25, 0.99, 1e-5
+    st = dict(E=E0.clone(), cs=torch.ones(K, device=dev), w=E0.clone())
+
+    def hip():
+        idx, out, counts, dw, loss, _ = ops.vq_train_assign(x, st["E"], cc)
+        searched = st["E"].clone()
+        ops.vq_train_update(st["cs"], st["w"], st["E"], counts, dw, decay, eps)
+        return ops.vq_train_backward(dout, x, searched, idx, dloss, cc)
+
+    parts = {"assign": lambda: ops.vq_train_assign(x, st["E"], cc)}
+    idx, out, counts, dw, loss, _ = ops.vq_train_assign(x, st["E"], cc)
+    parts["update"] = lambda: ops.vq_train_update(st["cs"], st["w"], st["E"], counts, dw, decay, eps)
+    parts["backward"] = lambda: ops.vq_train_backward(dout, x, st["E"], idx, dloss, cc)
+    ts = dict(E=E0.clone(), cs=torch.ones(K, device=dev), w=E0.clone())
+
+    def torch_ops():
+        flat = x.movedim(1, -1).reshape(-1, D)
+        dist = (flat ** 2).sum(1, keepdim=True) + (ts["E"].t() ** 2).sum(0, keepdim=True) - 2 * flat @ ts["E"].t()
+        i = torch.max(-dist, dim=1)[1]
+        enc = F.one_hot(i, K).float()
+        q = F.embedding(i, ts["E"])
+        ts["cs"].mul_(decay).add_(enc.sum(0) * (1 - decay))
+        n = ts["cs"].sum()
+        wk = (ts["cs"] + eps) / (n + K * eps) * n
+        ts["w"].mul_(decay).add_((flat.t() @ enc).t() * (1 - decay))
+        ts["E"].copy_(ts["w"] / wk[:, None])
+        loss_t = cc * F.mse_loss(q, flat)
+        dflat = dout.movedim(1, -1).reshape(-1, D) + (2 * cc / flat.numel()) * (flat - q) * dloss
+        return loss_t, dflat
+
+    rows = [("HIP assign + update + backward", timed(hip, reps))]
+    rows += [(f"  HIP {k} alone", timed(f, reps)) for k, f in parts.items()]
+    rows.append(("torch ops (one-hot, mm, EMA lines, mse_loss)", timed(torch_ops, reps)))
+    print(f"(B*S, D, K) = ({N}, {D}, {K}); median [min .. max] us over {reps} repetitions")
+    for name, (med, lo, hi) in rows:
+        print(f"  {name:<48s} {med:9.1f} [{lo:9.1f} .. {hi:9.1f}]")
+
+
+def full_step(dev, reps):
+    """One full training step at the README configuration (batch 1 of 64^3: the volume the test suite runs the README VQ-VAE on)
+    with the quantiser step timed inside it."""
+    from ddpm_ood_amd import ops
+    from ddpm_ood_amd.vqvae import VQVAE
+    from ddpm_ood_amd.vqvae_train import vqvae_forward_train
+
+    cfg = dict(spatial_dims=3, in_channels=1, out_channels=1, num_channels=(256,) * 4, num_res_layers=3,
+               num_res_channels=(256,) * 4, downsample_parameters=((2, 4, 1, 1),) * 4, upsample_parameters=((2, 4, 1, 1, 0),) * 4,
+               num_embeddings=2048, embedding_dim=128, decay=0.99)
+    torch.manual_seed(1)
+    m = VQVAE(**cfg).to(dev)
+    m.quantizer.quantizer.embedding.weight.requires_grad_(False)
+    params = [p for p in m.parameters() if p.requires_grad]
+    opt = torch.optim.Adam(params, lr=3e-4)
+    x = torch.rand(1, 1, 64, 64, 64, device=dev)
+    q_us = []
+    names = ("vq_train_assign", "vq_train_update", "vq_train_backward")
+    orig = {n: getattr(ops, n) for n in names}
+
+    def wrap(fn):
+        def inner(*a, **k):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            r = fn(*a, **k)
+            e.record()
+            q_us.append((s, e))
+            return r
+        return inner
+
+    for n in names:
+        setattr(ops, n, wrap(orig[n]))
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        r, ql = vqvae_forward_train(m, x)
+        (F.l1_loss(r, x) + ql).backward()
+        opt.step()
+
+    med, lo, hi = timed(step, reps, warmup=3)
+    torch.cuda.synchronize()
+    per_step = [sum(s.elapsed_time(e) for s, e in q_us[i: i + 3]) * 1e3 for i in range(3 * 3, len(q_us), 3)]
+    for n in names:
+        setattr(ops, n, orig[n])
+    qm = statistics.median(per_step)
+    print(f"full training step, README VQ-VAE, batch 1 of 64^3 (64 latent positions): median {med / 1e3:.2f} ms "
+          f"[{lo / 1e3:.2f} .. {hi / 1e3:.2f}] over {reps} steps; quantiser (3 HIP entry points) {qm:.1f} us = {100 * qm / med:.2f} % of the step")
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--full-step", type=int, default=1)
+    ap.add_argument("--quantiser", type=int, default=1, help="0: only the full step (e.g. under rocprofv3 --kernel-trace --stats)")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    if a.quantiser:
+        quantiser(2048, 128, 2048, a.reps, dev)   # batch 4 of 128^3 through four stride-2 levels: 4 x 8^3 latent positions
+        quantiser(16384, 128, 2048, a.reps, dev)
+    if a.full_step:
+        full_step(dev, max(5, a.reps // 5))
