@@ -790,6 +790,66 @@ def lpips_layer(f0, f1, lin, out=None):
     return out
 
 
+def lpips_layer_backward(f0, f1, lin, upstream, out=None, relu_mask: bool = True):
+    """Backward of lpips_layer w.r.t. f0: out (+)= upstream[n] d(score[n]) / d(f0[n]); relu_mask: f0 is a post-ReLU feature map and
+    out the gradient before that ReLU (0 where f0 <= 0, the accumulated value included)."""
+    lib = _lib.load()
+    f0 = require_device_f32(f0, "f0")
+    f1 = require_device_f32(f1, "f1")
+    lin = require_device_f32(lin, "lin")
+    upstream = require_device_f32(upstream, "upstream")
+    if f0.shape != f1.shape or f0.ndim != 4:
+        raise ValueError(f"feature maps differ in shape: {tuple(f0.shape)} vs {tuple(f1.shape)}")
+    N, Cc, H, W = f0.shape
+    if lin.numel() != Cc or upstream.numel() != N:
+        raise ValueError(f"lpips_layer_backward: lin has {lin.numel()} weights for {Cc} channels, upstream {upstream.numel()} for {N} pairs")
+    acc = out is not None
+    if out is None:
+        out = torch.empty_like(f0)
+    elif out.shape != f0.shape or not out.is_contiguous() or out.dtype != torch.float32 or out.device != f0.device:
+        raise ValueError("lpips_layer_backward: out must be a contiguous float32 tensor of f0's shape on its device")
+    check(lib.ddpm_lpips_layer_backward_f32(ptr(f0), ptr(f1), ptr(lin), ptr(upstream), ptr(out), N, Cc, H * W, int(acc),
+                                            int(relu_mask), stream_ptr()), "lpips_layer_backward")
+    return out
+
+
+def maxpool3s2_backward(x, dy, out=None, relu_mask: bool = False):
+    """Backward of maxpool3s2 (PyTorch's tie rule: the first maximum in row-major order takes the gradient): out (+)= dx;
+    relu_mask: 0 where x <= 0 (x is a post-ReLU feature map, out the gradient before that ReLU)."""
+    lib = _lib.load()
+    x = require_device_f32(x, "x")
+    dy = require_device_f32(dy, "dy")
+    N, Cc, H, W = x.shape
+    if tuple(dy.shape) != (N, Cc, (H - 3) // 2 + 1, (W - 3) // 2 + 1):
+        raise ValueError(f"maxpool3s2_backward: dy {tuple(dy.shape)} does not belong to x {tuple(x.shape)}")
+    acc = out is not None
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or not out.is_contiguous() or out.dtype != torch.float32 or out.device != x.device:
+        raise ValueError("maxpool3s2_backward: out must be a contiguous float32 tensor of x's shape on its device")
+    check(lib.ddpm_maxpool3s2_backward_f32(ptr(x), ptr(dy), ptr(out), N * Cc, H, W, int(acc), int(relu_mask), stream_ptr()),
+          "maxpool3s2_backward")
+    return out
+
+
+def lpips_conv1_dgrad(g, weight, in_channels: int, height: int, width: int, stride: int, pad: int, in_scale=None):
+    """Input gradient [N, in_channels (1 or 3), height, width] of lpips_conv(x, weight [Cout, 3, k, k], stride, pad, in_scale) given
+    g = the gradient of its pre-ReLU output; in_channels = 1: through the 1 -> 3 broadcast (the three channels summed)."""
+    lib = _lib.load()
+    g = require_device_f32(g, "g")
+    w = require_device_f32(weight, "weight")
+    cout, cin, k, _ = w.shape
+    N = g.shape[0]
+    Ho, Wo = (height + 2 * pad - k) // stride + 1, (width + 2 * pad - k) // stride + 1
+    if tuple(g.shape) != (N, cout, Ho, Wo):
+        raise ValueError(f"lpips_conv1_dgrad: g {tuple(g.shape)} is not the layer's output for a {height} x {width} input")
+    in_scale = None if in_scale is None else require_device_f32(in_scale, "in_scale")
+    out = torch.empty((N, in_channels, height, width), dtype=torch.float32, device=g.device)
+    check(lib.ddpm_lpips_conv1_dgrad_f32(ptr(g), ptr(w), ptr(in_scale), ptr(out), N, in_channels, cin, height, width, cout, k,
+                                         stride, pad, stream_ptr()), "lpips_conv1_dgrad")
+    return out
+
+
 def vq_nearest(x, codebook):
     """VQ-VAE quantiser, eval path: (indices int64 [B, *spatial], x + (codebook[indices] - x) [B, D, *spatial])."""
     lib = _lib.load()

@@ -233,6 +233,28 @@ def mse_loss_grad(pred, target):
     return loss, dpred
 
 
+def spectral_amp_grad(spec_r, spec_x, dloss=None, want_loss: bool = True, want_grad: bool = False):
+    """The elementwise half of the Jukebox spectral loss over two spectra [2 (re, im), ...]: (loss [1] or None, G [2, ...] or None)
+    with loss = mean((|R| - |X|)^2) (fp64 partial sums, fixed order) and G = (2 / n) dloss (|R| - |X|) R / |R| (0 where |R| = 0)."""
+    spec_r, spec_x = require_device_f32(spec_r, "spec_r"), require_device_f32(spec_x, "spec_x")
+    if spec_r.shape != spec_x.shape or spec_r.shape[0] != 2:
+        raise ValueError(f"spectral_amp_grad wants two equal [2, ...] spectra, got {tuple(spec_r.shape)} and {tuple(spec_x.shape)}")
+    lib = _lib.load()
+    n = spec_r[0].numel()
+    loss = partials = grad = None
+    if want_loss:
+        loss = _empty((1,), spec_r)
+        partials = torch.empty(lib.ddpm_spectral_partials(n), dtype=torch.float64, device=spec_r.device)
+    if want_grad:
+        grad = torch.empty_like(spec_r)
+    if dloss is not None:
+        dloss = require_device_f32(dloss, "dloss")
+    check(lib.ddpm_spectral_amp_grad_f32(ptr(spec_r[0]), ptr(spec_r[1]), ptr(spec_x[0]), ptr(spec_x[1]), ptr(dloss),
+                                         None if grad is None else ptr(grad[0]), None if grad is None else ptr(grad[1]),
+                                         ptr(loss), ptr(partials), n, 2.0 / n, stream_ptr()), "spectral_amp_grad")
+    return loss, grad
+
+
 def fill_(t, value: float):
     check(_lib.load().ddpm_fill_f32(ptr(t), value, t.numel(), stream_ptr()), "fill")
     return t

@@ -8,10 +8,12 @@ Adam at ``--vqvae_learning_rate``, epoch loop, five-key checkpoint dict, resume,
   * the encoder / decoder gradients go through PyTorch-ROCm autograd over ``encode_train`` / ``decode_train``: a differentiable
     ATen forward that evaluates the SAME parameter holders the HIP engine of ``vqvae.VQVAE`` reads (how the UNet's training step
     started before it went native; native k4-s2 / transposed weight-gradient kernels are the follow-up, DESIGN.md 8);
-  * the optimised loss is L1 + quantisation (commitment) loss.  The reference's other generator terms -- 0.001 x LPIPS, the
-    Jukebox spectral loss, the least-squares patch-adversarial loss -- and its discriminator are NOT built: ``--adversarial_weight``
-    / ``--adversarial_warmup`` are accepted, one loud warning names the missing terms, ``last_stats["missing_loss_terms"]`` records
-    them.
+  * the optimised loss is L1 + quantisation (commitment) loss by default.  ``DDPM_VQVAE_LOSS_TERMS`` (a comma list drawn from
+    ``perceptual``, ``spectral``; unknown names raise) adds the reference's 0.001 x LPIPS-AlexNet term and its Jukebox spectral
+    term, forward and backward on HIP kernels (``loss_terms.py``); ``DDPM_LPIPS_WEIGHTS=<state_dict file>`` loads
+    trained LPIPS weights (without it the seeded ones are used and a loud warning says so).  The least-squares patch-adversarial
+    loss and its discriminator are NOT built: ``--adversarial_weight`` / ``--adversarial_warmup`` are accepted, one loud warning
+    names what is still missing, ``last_stats["missing_loss_terms"]`` records it.
 Training never goes through ``VQVAE.forward`` or ``self.training`` (a fresh module has training=True and callers of the eval path
 do not always call .eval()): ``vqvae_forward_train`` is the training forward.
 Quirks of the reference: KEPT ``epoch_loss = sum of batch-mean losses / number of images`` (it picks the "best"
@@ -32,15 +34,21 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import _lib, loss_terms, ops
 from .data import get_data_loader
+from .perceptual import LPIPS
 from .vqvae import VQVAE, _ResidualUnit
 
 MISSING_LOSS_TERMS = ("perceptual (0.001 x LPIPS)", "Jukebox spectral", "patch-adversarial (and its discriminator)")
 CONFIG_KEYS = ("spatial_dims", "in_channels", "out_channels", "num_res_layers", "downsample_parameters", "upsample_parameters",
                "num_channels", "num_res_channels", "num_embeddings", "embedding_dim", "decay", "commitment_cost", "epsilon",
                "dropout", "ddp_sync")
+_TERM_OF_MISSING = ("perceptual", "spectral", None)  # the loss_terms name that builds MISSING_LOSS_TERMS[i]
 _WARNED = set()
+
+
+def _loss_text(head: str, terms, times: str = "") -> str:
+    return head + "".join({"perceptual": f" + 0.001 {times}perceptual", "spectral": " + spectral"}[t] for t in terms)
 
 
 def _all_reduce(flat: torch.Tensor) -> None:
@@ -199,12 +207,31 @@ class VQVAETrainer:
 
         self.adv_weight = args.adversarial_weight
         self.adversarial_warmup = bool(args.adversarial_warmup)
-        self.last_stats = {"missing_loss_terms": list(MISSING_LOSS_TERMS), "optimised_loss": "l1 + quantization"}
+        self.loss_terms = loss_terms.parse_terms(os.environ.get("DDPM_VQVAE_LOSS_TERMS"))
+        missing = [m for m, t in zip(MISSING_LOSS_TERMS, _TERM_OF_MISSING) if t not in self.loss_terms]
+        self.last_stats = {"missing_loss_terms": missing, "optimised_loss": _loss_text("l1 + quantization", self.loss_terms)}
+        self.last_terms = {}
         if "missing_terms" not in _WARNED:
             _WARNED.add("missing_terms")
-            print("WARNING: this VQ-VAE trainer optimises L1 + quantisation loss ONLY.  NOT built: " + "; ".join(MISSING_LOSS_TERMS)
+            what = _loss_text("L1 + quantisation", self.loss_terms, "x ") + (" loss" if self.loss_terms else " loss ONLY")
+            print(f"WARNING: this VQ-VAE trainer optimises {what}.  NOT built: " + "; ".join(missing)
                   + f".  --adversarial_weight {self.adv_weight} / --adversarial_warmup {int(self.adversarial_warmup)} are accepted "
                   "and have no effect; a checkpoint trained here is not the reference's recipe.", file=sys.stderr, flush=True)
+        self.lpips = None
+        if "perceptual" in self.loss_terms:
+            self.lpips = LPIPS().to(self.device)
+            weights = os.environ.get("DDPM_LPIPS_WEIGHTS")
+            if weights:
+                sd = torch.load(weights, map_location="cpu", weights_only=True)
+                self.lpips.load_pretrained_state_dict(sd.get("state_dict", sd) if isinstance(sd, dict) else sd)
+                self.lpips.to(self.device)
+                print(f"Loaded LPIPS weights from {weights}.")
+            elif "lpips_weights" not in _WARNED:
+                _WARNED.add("lpips_weights")
+                print("WARNING: DDPM_LPIPS_WEIGHTS is not set: the perceptual term runs on SEEDED SYNTHETIC LPIPS-AlexNet weights "
+                      "(the trained ones need the network).  It is then NOT the reference's perceptual loss: the arithmetic is, "
+                      "the metric is not.", file=sys.stderr, flush=True)
+            self.last_stats["lpips_pretrained"] = bool(self.lpips.pretrained)
 
         # embedding.weight is moved by the EMA update only: no gradient, not an optimiser parameter
         codebook = self.model.quantizer.quantizer.embedding.weight
@@ -245,6 +272,13 @@ class VQVAETrainer:
         self.train_loader = get_data_loader(args.training_ids, rank=self.rank, world=self.world, **kw)
         self.val_loader = get_data_loader(args.validation_ids, rank=self.rank, world=self.world, **kw)
         self.history = []  # (epoch, epoch loss, mean L1)
+        self._epoch = self._step = 0  # what the 2.5-D perceptual term's slice draw is seeded with, beside the seed
+        if self.lpips is not None:
+            src = self.train_loader.images
+            first = src[0] if len(src) else None
+            if first is not None and min(first.shape[1:]) < loss_terms.MIN_LPIPS_SIZE:
+                raise ValueError(f"DDPM_VQVAE_LOSS_TERMS=perceptual needs spatial sizes >= {loss_terms.MIN_LPIPS_SIZE} (AlexNet's "
+                                 f"second max-pool is empty below), the training images are {tuple(first.shape[1:])}")
 
     def _broadcast_initial_state(self):
         """Every rank starts from rank 0's parameters and buffers (DistributedDataParallel's constructor in the reference)."""
@@ -276,15 +310,38 @@ class VQVAETrainer:
             g.copy_(flat[off: off + g.numel()].view_as(g))
             off += g.numel()
 
+    def extra_terms(self, reconstruction: torch.Tensor, images: torch.Tensor):
+        """The enabled terms of DDPM_VQVAE_LOSS_TERMS as the generator loss adds them: (their weighted sum or None, {name: the
+        unweighted value as a detached device scalar}).  Local to this rank's batch: the flat-gradient all_reduce carries them."""
+        total, values = None, {}
+        for name in self.loss_terms:
+            if name == "perceptual":
+                idx = None
+                if self.spatial_dimension == 3:
+                    idx = loss_terms.fake3d_slice_indices(images.shape, self.seed + self.rank, self._epoch, self._step)
+                v = loss_terms.perceptual_term(self.lpips, reconstruction.float(), images.float(), self.spatial_dimension, idx)
+                w = loss_terms.PERCEPTUAL_WEIGHT
+            else:
+                v = loss_terms.spectral_term(reconstruction.float(), images.float())
+                w = loss_terms.SPECTRAL_WEIGHT
+            values[name] = v.detach()
+            total = w * v if total is None else total + w * v
+        return total, values
+
     def train_step(self, images: torch.Tensor):
-        """One optimisation step on a device batch -> (total loss, L1, quantisation loss) as device scalars."""
+        """One optimisation step on a device batch -> (total loss, L1, quantisation loss) as device scalars; the values of the
+        enabled extra terms (unweighted) go to ``self.last_terms``."""
         self.optimizer.zero_grad(set_to_none=True)
         reconstruction, quantization_loss = vqvae_forward_train(self.model, images, update_codebook=True)
         recons_loss = F.l1_loss(reconstruction.float(), images.float())
         total = recons_loss + quantization_loss
+        if self.loss_terms:
+            extra, self.last_terms = self.extra_terms(reconstruction, images)
+            total = total + extra
         total.backward()
         self._sync_grads()
         self.optimizer.step()
+        self._step += 1
         return total.detach(), recons_loss.detach(), quantization_loss.detach()
 
     def train_epoch(self, epoch: int) -> float:
@@ -300,6 +357,8 @@ class VQVAETrainer:
         bs = self.train_loader.batch_size
         src = self.train_loader.images
         losses, l1s, sizes = [], [], []
+        terms = {t: [] for t in self.loss_terms}
+        self._epoch, self._step = epoch, 0
         t0 = time.time()
         for s in range(0, len(order), bs):
             idx = order[s: s + bs]
@@ -307,6 +366,8 @@ class VQVAETrainer:
             total, l1, _q = self.train_step(images)
             losses.append(total.item())
             l1s.append(l1.item())
+            for t in terms:
+                terms[t].append(self.last_terms[t].item())
             sizes.append(images.shape[0])
             self.global_step += images.shape[0]
             if self.quick_test:
@@ -316,7 +377,11 @@ class VQVAETrainer:
         perplexity = float(self.model.quantizer.perplexity)
         self.last_stats.update(epoch=epoch, epoch_loss=epoch_loss, l1=mean_l1, perplexity=perplexity)
         self.history.append((epoch, epoch_loss, mean_l1))
-        print(f"Epoch {epoch}: loss {epoch_loss:.6f} (sum of batch means / images), L1 {mean_l1:.6f}, perplexity "
+        extra = ""
+        for t, vals in terms.items():
+            self.last_stats[t] = sum(vals) / max(len(vals), 1)
+            extra += f", {t} {self.last_stats[t]:.6f}"
+        print(f"Epoch {epoch}: loss {epoch_loss:.6f} (sum of batch means / images), L1 {mean_l1:.6f}{extra}, perplexity "
               f"{perplexity:.2f} ({time.time() - t0:.1f} s)")
         return epoch_loss
 
@@ -326,13 +391,17 @@ class VQVAETrainer:
         for batch in self.val_loader:
             images = batch["image"].to(self.device)
             reconstruction, quantization_loss = vqvae_forward_train(self.model, images, update_codebook=False)
-            tot += (F.l1_loss(reconstruction.float(), images.float()) + quantization_loss).item()
+            loss = F.l1_loss(reconstruction.float(), images.float()) + quantization_loss
+            if self.loss_terms:  # the reference validates on the generator loss
+                self._step = n
+                loss = loss + self.extra_terms(reconstruction, images)[0]
+            tot += loss.item()
             n += 1
             if self.quick_test:
                 break
         val = tot / max(n, 1)
         self.last_stats["val_loss"] = val
-        print(f"Validation {epoch}: L1 + quantisation loss {val:.6f}")
+        print(f"Validation {epoch}: {_loss_text('L1 + quantisation', self.loss_terms)} loss {val:.6f}")
         return val
 
     def save_checkpoint(self, path, epoch, save_message=None):

@@ -398,6 +398,41 @@ int ddpm_lpips_layer_f32(const float *f0, const float *f1, const float *lin, flo
                          int accumulate, ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Loss terms of VQ-VAE training (src/trainers/vqvae_trainer.py: 0.001 x PerceptualLoss + JukeboxLoss in the generator loss;
+ * SURVEY.md A.8).  Entry points added without an ABI bump.  Everything is deterministic (fixed-order sums, no atomics).
+ * ---------------------------------------------------------------------------------- */
+/* Backward of ddpm_lpips_layer_f32 with respect to f0: df0[n] (+)= upstream[n] * d(out[n]) / d(f0[n]); f1 and lin are
+ * constants.  With u = f0 / (|f0| + 1e-10) over channels and g_c = (2 upstream / HW) lin_c (u_c - v_c):
+ * df0_k = g_k / (|f0| + 1e-10) - (sum_c g_c f0_c) f0_k / (|f0| (|f0| + 1e-10)^2); the second term is 0 where |f0| = 0.
+ * relu_mask != 0: f0 is a post-ReLU feature map and df0 the gradient BEFORE that ReLU: the value written (the accumulated
+ * one included) is 0 where f0 <= 0.  N <= 65 535.                                                                         */
+int ddpm_lpips_layer_backward_f32(const float *f0, const float *f1, const float *lin, const float *upstream, float *df0, int N,
+                                  int C, int HW, int accumulate, int relu_mask, ddpm_stream_t stream);
+
+/* Backward of ddpm_maxpool3s2_f32, gather form: dx[h, w] (+)= the sum of dy over the <= 4 windows that cover (h, w) and whose
+ * FIRST maximum in row-major scan order it is (PyTorch's tie rule).  x: the pool's input [planes, H, W]; dy: [planes, Ho, Wo].
+ * relu_mask as above, on x.                                                                                               */
+int ddpm_maxpool3s2_backward_f32(const float *x, const float *dy, float *dx, int64_t planes, int H, int W, int accumulate,
+                                 int relu_mask, ddpm_stream_t stream);
+
+/* Input gradient of ddpm_lpips_conv_f32 for the strided first layer (Cin = 3; AlexNet: k 11, stride 4, pad 2), through the
+ * folded input affine and the 1 -> 3 broadcast: dx[N, Cx, H, W] (overwritten) from g[N, Cout, Ho, Wo] (the gradient before the
+ * layer's ReLU already applied).  Cx = 3: dx_c = in_scale[c] * (w_c correlated with g); Cx = 1: the sum of the three.  Rows and
+ * columns no window covers get exact zeros.  in_scale may be NULL (ones).                                                  */
+int ddpm_lpips_conv1_dgrad_f32(const float *g, const float *w, const float *in_scale, float *dx, int N, int Cx, int Cin, int H,
+                               int W, int Cout, int k, int stride, int pad, ddpm_stream_t stream);
+
+/* The elementwise half of the Jukebox spectral loss mean((|R| - |X|)^2) over n spectrum elements given as re / im planes
+ * (rr, ri of the reconstruction, xr, xi of the image; the ortho-normalised DFTs are dense per-axis products on ddpm_gemm_f32).
+ * loss != NULL: loss[0] = the mean, from per-workgroup fp64 partial sums (partials: ddpm_spectral_partials(n) doubles of
+ * scratch) folded in a fixed order.  gr != NULL: the spectrum-side gradient G = scale * dloss[0] * (|R| - |X|) * R / |R| into
+ * gr / gi (they may alias rr / ri), 0 where |R| = 0 (autograd gives NaN there); dloss NULL: 1; the caller passes scale = 2 / n.
+ * The transform is unitary: the gradient with respect to the reconstruction is the real part of the inverse DFT of G.      */
+size_t ddpm_spectral_partials(int64_t n);
+int ddpm_spectral_amp_grad_f32(const float *rr, const float *ri, const float *xr, const float *xi, const float *dloss, float *gr,
+                               float *gi, float *loss, double *partials, int64_t n, float scale, ddpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * UNet engine: DiffusionModelUNet(x, timesteps) as one native call
  * (ctor kwargs: src/trainers/base.py:66-86; call: src/trainers/reconstruct.py:151-153).
  * ---------------------------------------------------------------------------------- */

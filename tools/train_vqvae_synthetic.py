@@ -4,8 +4,13 @@
 evidence tool; log kept under profiles/).
 
     python tools/train_vqvae_synthetic.py [--epochs 30] [--n_train 256] [--out /tmp/vqvae_synth]
+                                          [--loss_terms perceptual,spectral] [--vqvae_only 1]
+
+--loss_terms sets DDPM_VQVAE_LOSS_TERMS for the run (the perceptual and spectral terms of the generator loss); --vqvae_only 1
+stops after the VQ-VAE (the with / without comparison of profiles/vqvae_training.md).
 """
 import argparse
+import os
 import sys
 import time
 from pathlib import Path
@@ -21,7 +26,11 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=32)
     ap.add_argument("--out", default="/tmp/vqvae_synth")
+    ap.add_argument("--loss_terms", default=None, help="DDPM_VQVAE_LOSS_TERMS for this run (default: the environment's)")
+    ap.add_argument("--vqvae_only", type=int, default=0)
     a = ap.parse_args()
+    if a.loss_terms is not None:
+        os.environ["DDPM_VQVAE_LOSS_TERMS"] = a.loss_terms
     import reconstruct as rcli
     import train_ddpm
     import train_vqvae
@@ -41,11 +50,13 @@ def main():
     t0 = time.time()
     tr = VQVAETrainer(vargs)
     tr.train(vargs)
-    print(f"trained {a.epochs} epochs in {time.time() - t0:.1f} s; L1 {tr.history[0][2]:.5f} -> {tr.history[-1][2]:.5f}; "
-          f"final perplexity {tr.last_stats['perplexity']:.2f} of {vargs.vqvae_num_embeddings} codes; best epoch loss {tr.best_loss:.6f}")
+    print(f"trained {a.epochs} epochs ({tr.last_stats['optimised_loss']}) in {time.time() - t0:.1f} s; L1 {tr.history[0][2]:.5f} -> "
+          f"{tr.history[-1][2]:.5f}; final perplexity {tr.last_stats['perplexity']:.2f} of {vargs.vqvae_num_embeddings} codes; best epoch loss {tr.best_loss:.6f}")
     ckpt = str(Path(a.out) / "vqvae_synthetic" / "checkpoint.pth")
     del tr
     torch.cuda.empty_cache()
+    if a.vqvae_only:
+        return
 
     sched = ["--beta_schedule", "scaled_linear_beta", "--beta_start", "0.0015", "--beta_end", "0.0195"]
     common = ["--output_dir", a.out, "--model_name", "ldm_synthetic", "--is_grayscale", "1", "--vqvae_checkpoint", ckpt]

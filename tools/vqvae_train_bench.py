@@ -2,7 +2,11 @@
 device (one-hot, mm, EMA lines, mse_loss) -- same process, same box, medians of event-timed repetitions.  Results:
 profiles/vqvae_training.md.
 
-    python tools/vqvae_train_bench.py [--reps 50] [--full-step 1]
+    python tools/vqvae_train_bench.py [--reps 50] [--full-step 1] [--terms 1]
+
+--terms 1 also times the perceptual and the spectral term of DDPM_VQVAE_LOSS_TERMS (forward + backward w.r.t. the reconstruction)
+at the README configuration -- one 64^3 volume, 2.5-D LPIPS over three axes with half the slices kept -- on the HIP kernels and
+through PyTorch-ROCm autograd (torch.fft, F.conv2d, F.max_pool2d), and the full training step with both terms.
     rocprofv3 --kernel-trace --stats -d out -o step -- python tools/vqvae_train_bench.py --quantiser 0 --reps 25
 """
 import argparse
@@ -75,9 +79,69 @@ def quantiser(N, D, K, reps, dev):
         print(f"  {name:<48s} {med:9.1f} [{lo:9.1f} .. {hi:9.1f}]")
 
 
-def full_step(dev, reps):
+def _aten_lpips(lp, in0, in1):
+    """LPIPS(normalize=False) over the module's own weights with ATen ops and autograd (the baseline of --terms)."""
+    def feats(x):
+        x = (x.expand(-1, 3, -1, -1) - lp.scaling_layer.shift) / lp.scaling_layer.scale
+        net, out = lp.net, []
+        for k, (conv, pool) in enumerate(((net.slice1[0], False), (net.slice2[1], True), (net.slice3[1], True), (net.slice4[0], False),
+                                          (net.slice5[0], False))):
+            if pool:
+                x = F.max_pool2d(x, 3, 2)
+            x = F.relu(F.conv2d(x, conv.weight, conv.bias, stride=conv.stride, padding=conv.padding))
+            out.append(x)
+        return out
+    norm = lambda f: f / (torch.sqrt((f ** 2).sum(1, keepdim=True)) + 1e-10)  # noqa: E731
+    val = 0
+    for k, (a, b) in enumerate(zip(feats(in0), feats(in1))):
+        val = val + (lp.lins[k].model[1].weight * (norm(a) - norm(b)) ** 2).sum(1).mean((1, 2))
+    return val
+
+
+def loss_terms_bench(dev, reps):
+    """Each term's forward + backward on one 64^3 volume: HIP kernels against PyTorch-ROCm autograd, same process."""
+    from ddpm_ood_amd import loss_terms
+    from ddpm_ood_amd.perceptual import LPIPS
+
+    g = torch.Generator().manual_seed(1)
+    x = torch.rand(1, 1, 64, 64, 64, generator=g).to(dev)
+    r = (0.8 * x + 0.1 + 0.05 * torch.randn(x.shape, generator=g).to(dev)).requires_grad_(True)
+    lp = LPIPS().to(dev)
+    idx = [i.to(dev) for i in loss_terms.fake3d_slice_indices(x.shape, 1, 0, 0)]
+
+    def run(fn):
+        def inner():
+            r.grad = None
+            fn().backward()
+        return inner
+
+    def aten_perceptual():
+        total = 0
+        for perm, i in zip(loss_terms._VIEWS, idx):
+            rs, xs = r.permute(*perm), x.permute(*perm)
+            total = total + _aten_lpips(lp, rs.reshape(-1, *rs.shape[2:])[i], xs.reshape(-1, *xs.shape[2:])[i]).mean()
+        return total
+
+    def aten_spectral():
+        a = lambda t: torch.fft.fftn(t, dim=(1, 2, 3, 4), norm="ortho").abs()  # noqa: E731
+        return ((a(r) - a(x)) ** 2).mean()
+
+    rows = [("perceptual, HIP (3 x 32 slices of 64 x 64)", run(lambda: loss_terms.perceptual_term(lp, r, x, 3, idx))),
+            ("perceptual, ATen autograd", run(aten_perceptual)),
+            ("spectral, HIP (dense DFT on train_ops.gemm)", run(lambda: loss_terms.spectral_term(r, x))),
+            ("spectral, ATen autograd (torch.fft)", run(aten_spectral))]
+    vals = [float(f().detach()) for f in (lambda: loss_terms.perceptual_term(lp, r, x, 3, idx), aten_perceptual,
+                                 lambda: loss_terms.spectral_term(r, x), aten_spectral)]
+    print(f"loss terms, forward + backward on one 64^3 volume; median [min .. max] us over {reps} repetitions (values: perceptual "
+          f"{vals[0]:.6e} / {vals[1]:.6e}, spectral {vals[2]:.6e} / {vals[3]:.6e})")
+    for name, fn in rows:
+        med, lo, hi = timed(fn, reps)
+        print(f"  {name:<48s} {med:9.1f} [{lo:9.1f} .. {hi:9.1f}]")
+
+
+def full_step(dev, reps, terms=()):
     """One full training step at the README configuration (batch 1 of 64^3: the volume the test suite runs the README VQ-VAE on)
-    with the quantiser step timed inside it."""
+    with the quantiser step timed inside it; terms: the extra loss terms of DDPM_VQVAE_LOSS_TERMS, timed inside it too."""
     from ddpm_ood_amd import ops
     from ddpm_ood_amd.vqvae import VQVAE
     from ddpm_ood_amd.vqvae_train import vqvae_forward_train
@@ -107,11 +171,22 @@ def full_step(dev, reps):
 
     for n in names:
         setattr(ops, n, wrap(orig[n]))
+    if terms:
+        from ddpm_ood_amd import loss_terms
+        from ddpm_ood_amd.perceptual import LPIPS
+
+        lp = LPIPS().to(dev)
+        idx = loss_terms.fake3d_slice_indices(x.shape, 1, 0, 0)
 
     def step():
         opt.zero_grad(set_to_none=True)
         r, ql = vqvae_forward_train(m, x)
-        (F.l1_loss(r, x) + ql).backward()
+        loss = F.l1_loss(r, x) + ql
+        if "perceptual" in terms:
+            loss = loss + loss_terms.PERCEPTUAL_WEIGHT * loss_terms.perceptual_term(lp, r, x, 3, idx)
+        if "spectral" in terms:
+            loss = loss + loss_terms.spectral_term(r, x)
+        loss.backward()
         opt.step()
 
     med, lo, hi = timed(step, reps, warmup=3)
@@ -120,7 +195,7 @@ def full_step(dev, reps):
     for n in names:
         setattr(ops, n, orig[n])
     qm = statistics.median(per_step)
-    print(f"full training step, README VQ-VAE, batch 1 of 64^3 (64 latent positions): median {med / 1e3:.2f} ms "
+    print(f"full training step ({' + '.join(('l1', 'quantisation') + tuple(terms))}), README VQ-VAE, batch 1 of 64^3 (64 latent positions): median {med / 1e3:.2f} ms "
           f"[{lo / 1e3:.2f} .. {hi / 1e3:.2f}] over {reps} steps; quantiser (3 HIP entry points) {qm:.1f} us = {100 * qm / med:.2f} % of the step")
 
 
@@ -129,6 +204,7 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--full-step", type=int, default=1)
     ap.add_argument("--quantiser", type=int, default=1, help="0: only the full step (e.g. under rocprofv3 --kernel-trace --stats)")
+    ap.add_argument("--terms", type=int, default=0, help="1: time the perceptual and spectral loss terms, alone and inside the step")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.quantiser:
@@ -136,3 +212,7 @@ if __name__ == "__main__":
         quantiser(16384, 128, 2048, a.reps, dev)
     if a.full_step:
         full_step(dev, max(5, a.reps // 5))
+    if a.terms:
+        loss_terms_bench(dev, max(5, a.reps // 5))
+        for terms in (("perceptual",), ("spectral",), ("perceptual", "spectral")):
+            full_step(dev, max(5, a.reps // 5), terms)

@@ -6,8 +6,10 @@ reference's train_vqvae.py, so the README's command keeps working.
         --image_size=128 --vqvae_num_embeddings=2048 --vqvae_embedding_dim=128
     torchrun --nproc_per_node=8 --master-addr 127.0.0.1 train_vqvae.py ...   # one rank per MI355X
 
-The optimised loss is L1 + quantisation loss; --adversarial_weight / --adversarial_warmup are accepted, and the trainer says
-loudly which of the reference's loss terms are not built (ddpm_ood_amd/vqvae_train.py).
+The optimised loss is L1 + quantisation loss; DDPM_VQVAE_LOSS_TERMS=perceptual,spectral (environment, no flag) adds the
+reference's 0.001 x LPIPS and Jukebox spectral terms on HIP kernels, DDPM_LPIPS_WEIGHTS=<state_dict file> loads trained LPIPS
+weights.  --adversarial_weight / --adversarial_warmup are accepted, and the trainer says loudly which of the reference's loss
+terms are not built (ddpm_ood_amd/vqvae_train.py).
 """
 
 import argparse
