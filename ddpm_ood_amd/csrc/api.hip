@@ -48,6 +48,9 @@ static void load_switches() {
   n.conv_d3s = env_int("DDPM_CONV_D3S", 1);
   n.d1s_maxpx = env_int("DDPM_D1S_MAXPX", 16384);
   n.conv_splitk = env_int("DDPM_CONV_SPLITK", 1) != 0;
+  n.conv_winograd = env_int("DDPM_CONV_WINOGRAD", 1) != 0;
+  n.linear_skinny = env_int("DDPM_LINEAR_SKINNY", 1) != 0;
+  n.conv1x1_dma = env_int("DDPM_CONV1X1_DMA", 1) != 0;
   n.gn_fused = env_int("DDPM_GN_FUSED", 1) != 0;
   n.attn_waves8 = env_int("DDPM_ATTN_WAVES", 8) != 4;
   n.convin_fast = env_int("DDPM_CONVIN_FAST", 1) != 0;

@@ -54,6 +54,9 @@ struct Switches {
   int attn_fa = 1;              // DDPM_ATTN_FA (0: the LDS-exchange kernels of attention.hip also when scratch is given; 2: the
                                 // register-resident kernel for every multiple of 64 tokens, not only from 1 024)
   bool conv_splitk = true;      // DDPM_CONV_SPLITK
+  bool conv_winograd = true;    // DDPM_CONV_WINOGRAD: 0 never the F(2x2) kernels (conv_wino.hip)
+  bool linear_skinny = true;    // DDPM_LINEAR_SKINNY
+  bool conv1x1_dma = true;      // DDPM_CONV1X1_DMA
   bool gn_fused = true;         // DDPM_GN_FUSED
   bool attn_waves8 = true;      // DDPM_ATTN_WAVES: 4 selects the four-wave split-f16 attention kernel
   bool convin_fast = true;      // DDPM_CONVIN_FAST
@@ -212,59 +215,74 @@ __device__ __forceinline__ float block_sum_256(float v, float *red) {
 }
 
 // ---- internal launchers shared between api.hip and the UNet engine ---------------------
+int device_cus();
+// conv_dispatch.hip: the ordered table of the families below -- the selection exists there and nowhere else
 int conv_dispatch(const ddpm_conv_desc &d, hipStream_t s);
-bool conv_mfma_supported(const ddpm_conv_desc &d);
-int launch_conv_mfma(const ddpm_conv_desc &d, hipStream_t s);
-int launch_conv_direct(const ddpm_conv_desc &d, hipStream_t s);
-size_t packed_conv_weight_floats(int Cout, int Cin, int ksize);
-size_t folded_upsample_weight_floats(int Cout, int Cin);
-bool conv1x1_dma_supported(const ddpm_conv_desc &d);
-int launch_conv1x1_dma(const ddpm_conv_desc &d, hipStream_t s);
-size_t conv1x1_h_weight_halves(int Cout, int Cin);
-int launch_pack_conv1x1_h_weight(const float *w_raw, uint16_t *dst, int Cout, int Cin, int cout_offset, int Cout_total,
-                                 hipStream_t s);
+size_t conv_scratch_floats(const ddpm_conv_desc &d);  // what conv_dispatch can use: the largest of the kernels' needs
+int conv_stats_parts(const ddpm_conv_desc &d);
+// Per family: <f>_supported (does it take d), launch_<f>, <f>_scratch_floats (its own split, 0: none), <f>_stats_parts (slices of
+// desc.stats_out its epilogue writes, 0: none), then its weight forms.
+// linear_skinny.hip
 bool linear_skinny_supported(const ddpm_conv_desc &d);
 int launch_linear_skinny(const ddpm_conv_desc &d, hipStream_t s);
-bool conv_wino_supported(const ddpm_conv_desc &d);
-int launch_conv_wino(const ddpm_conv_desc &d, hipStream_t s);
-size_t wino_weight_floats(int Cout, int Cin);
-size_t conv_wino_scratch_floats(const ddpm_conv_desc &d);
-int launch_wino_split_reduce(const ddpm_conv_desc &d, int S, long long pstride, int HW, hipStream_t s);
-int wino_split_reduce_stats_parts(int HW);  // slices of desc.stats_out the reduce pass writes for planes of HW floats (0: none)
-size_t conv_wino44_scratch_floats(const ddpm_conv_desc &d);
-size_t conv_mfma_scratch_floats(const ddpm_conv_desc &d);
-size_t conv_scratch_floats(const ddpm_conv_desc &d);  // what conv_dispatch can use: the largest of the kernels' needs
-bool conv_wino44_supported(const ddpm_conv_desc &d);
-int launch_conv_wino44(const ddpm_conv_desc &d, hipStream_t s);
-size_t wino44_weight_floats(int Cout, int Cin);
-bool conv_wino44h_supported(const ddpm_conv_desc &d);
-int launch_conv_wino44h(const ddpm_conv_desc &d, hipStream_t s);
-size_t conv_wino44h_scratch_floats(const ddpm_conv_desc &d);
+// conv_d3s.hip: d3s (3x3), d3s2 (3x3 stride 2; statistics as d3s), d1s (1x1)
+bool conv_d3s_supported(const ddpm_conv_desc &d);
+int launch_conv_d3s(const ddpm_conv_desc &d, hipStream_t s);
+size_t conv_d3s_scratch_floats(const ddpm_conv_desc &d);
+int conv_d3s_stats_parts(const ddpm_conv_desc &d);
 bool conv_d3s2_supported(const ddpm_conv_desc &d);
 int launch_conv_d3s2(const ddpm_conv_desc &d, hipStream_t s);
 size_t conv_d3s2_scratch_floats(const ddpm_conv_desc &d);
 bool conv_d1s_supported(const ddpm_conv_desc &d);
 int launch_conv_d1s(const ddpm_conv_desc &d, hipStream_t s);
 size_t conv_d1s_scratch_floats(const ddpm_conv_desc &d);
-size_t conv_d1s_weight_halves(int Cout, int Cin);
-int launch_pack_conv_d1s_weight(const float *w_raw, uint16_t *dst, int Cout, int Cin, int cout_offset, int Cout_total, hipStream_t s);
-bool conv_d3s_supported(const ddpm_conv_desc &d);
-int launch_conv_d3s(const ddpm_conv_desc &d, hipStream_t s);
-size_t conv_d3s_scratch_floats(const ddpm_conv_desc &d);
-int conv_d3s_stats_parts(const ddpm_conv_desc &d);
-int conv_s2h_stats_parts(const ddpm_conv_desc &d);
-int device_cus();
 size_t conv_d3h_weight_halves(int Cout, int Cin);
 int launch_pack_conv_d3h_weight(const float *w_raw, uint16_t *dst, int Cout, int Cin, hipStream_t s);
-bool conv_s2h_supported(const ddpm_conv_desc &d);
-int launch_conv_s2h(const ddpm_conv_desc &d, hipStream_t s);
-size_t conv_s2h_weight_halves(int Cout, int Cin);
-int launch_pack_conv_s2h_weight(const float *w_raw, uint16_t *dst, int Cout, int Cin, hipStream_t s);
+size_t conv_d1s_weight_halves(int Cout, int Cin);
+int launch_pack_conv_d1s_weight(const float *w_raw, uint16_t *dst, int Cout, int Cin, int cout_offset, int Cout_total, hipStream_t s);
+// conv_wino44h.hip
+bool conv_wino44h_supported(const ddpm_conv_desc &d);
+int launch_conv_wino44h(const ddpm_conv_desc &d, hipStream_t s);
+size_t conv_wino44h_scratch_floats(const ddpm_conv_desc &d);
 int conv_wino44h_stats_parts(const ddpm_conv_desc &d);
-int conv_wino_stats_parts(const ddpm_conv_desc &d);
-int conv_stats_parts(const ddpm_conv_desc &d);
 size_t wino44h_weight_halves(int Cout, int Cin);
 int launch_pack_wino44h_weight(const float *w_raw, uint16_t *w_wino44h, int Cout, int Cin, hipStream_t s, int nkd = 1);
+// conv_wino44.hip
+bool conv_wino44_supported(const ddpm_conv_desc &d);
+int launch_conv_wino44(const ddpm_conv_desc &d, hipStream_t s);
+size_t conv_wino44_scratch_floats(const ddpm_conv_desc &d);
+size_t wino44_weight_floats(int Cout, int Cin);
+// conv_wino.hip (+ the reduce pass every channel-split launch ends with)
+bool conv_wino_supported(const ddpm_conv_desc &d);
+int launch_conv_wino(const ddpm_conv_desc &d, hipStream_t s);
+size_t conv_wino_scratch_floats(const ddpm_conv_desc &d);
+int conv_wino_stats_parts(const ddpm_conv_desc &d);
+size_t wino_weight_floats(int Cout, int Cin);
+int launch_wino_split_reduce(const ddpm_conv_desc &d, int S, long long pstride, int HW, hipStream_t s);
+int wino_split_reduce_stats_parts(int HW);  // slices of desc.stats_out the reduce pass writes for planes of HW floats (0: none)
+// conv_s2h.hip
+bool conv_s2h_supported(const ddpm_conv_desc &d);
+int launch_conv_s2h(const ddpm_conv_desc &d, hipStream_t s);
+int conv_s2h_stats_parts(const ddpm_conv_desc &d);
+size_t conv_s2h_weight_halves(int Cout, int Cin);
+int launch_pack_conv_s2h_weight(const float *w_raw, uint16_t *dst, int Cout, int Cin, hipStream_t s);
+// conv1x1_dma.hip
+bool conv1x1_dma_supported(const ddpm_conv_desc &d);
+int launch_conv1x1_dma(const ddpm_conv_desc &d, hipStream_t s);
+size_t conv1x1_h_weight_halves(int Cout, int Cin);
+int launch_pack_conv1x1_h_weight(const float *w_raw, uint16_t *dst, int Cout, int Cin, int cout_offset, int Cout_total,
+                                 hipStream_t s);
+// conv_mfma.hip
+bool conv_mfma_supported(const ddpm_conv_desc &d);
+int launch_conv_mfma(const ddpm_conv_desc &d, hipStream_t s);
+size_t conv_mfma_scratch_floats(const ddpm_conv_desc &d);
+size_t packed_conv_weight_floats(int Cout, int Cin, int ksize);
+size_t folded_upsample_weight_floats(int Cout, int Cin);
+// conv_direct.hip
+bool conv_direct_supported(const ddpm_conv_desc &d);
+int launch_conv_direct(const ddpm_conv_desc &d, hipStream_t s);
+int conv_direct_stats_parts(const ddpm_conv_desc &d);
+// weight packers of the families above
 int launch_pack_wino44_weight(const float *w_raw, float *w_wino44, int Cout, int Cin, hipStream_t s, int nkd = 1);
 int launch_pack_wino_weight(const float *w_raw, float *w_wino, int Cout, int Cin, hipStream_t s, int nkd = 1);
 int launch_fold_upsample_weight(const float *w_raw, float *w_folded, int Cout, int Cin, hipStream_t s);

@@ -66,10 +66,9 @@ static bool conv1x1_f16x3_enabled() {
 }
 
 bool conv1x1_dma_supported(const ddpm_conv_desc &d) {
-  static const bool enabled = !(getenv("DDPM_CONV1X1_DMA") && atoi(getenv("DDPM_CONV1X1_DMA")) == 0);
   const int Cin = d.C1 + d.C2;
   const long HW = (long)d.Ho * d.Wo;
-  if (!enabled || d.force_direct || !d.w_packed) return false;
+  if (!sw().conv1x1_dma || d.force_direct || !d.w_packed) return false;
   if (d.ksize != 1 || d.mode != DDPM_CONV_NORMAL || d.act != DDPM_ACT_NONE) return false;
   // GroupNorm prologue: split-f16 form only; a 64-pixel group of a tile belongs to one image
   if (d.gscale && (!conv1x1_f16x3_enabled() || !d.gshift || HW % 64)) return false;

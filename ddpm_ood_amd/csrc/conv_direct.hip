@@ -466,90 +466,13 @@ int launch_conv_direct(const ddpm_conv_desc &d, hipStream_t s) {
   return 0;
 }
 
-size_t conv_scratch_floats(const ddpm_conv_desc &d) {
-  const bool vol = d.dims == 3 || d.Di > 1 || d.Do > 1;  // the Winograd splits are 2-D only
-  const size_t a = vol ? 0 : conv_wino44_scratch_floats(d), b = vol ? 0 : conv_wino_scratch_floats(d);
-  const size_t c = linear_skinny_supported(d) ? 0 : conv_mfma_scratch_floats(d);
-  const size_t h = vol ? 0 : conv_wino44h_scratch_floats(d);
-  const size_t ab = (a > b ? a : b) > h ? (a > b ? a : b) : h;
-  const size_t e1 = vol ? 0 : conv_d3s_scratch_floats(d), e2 = vol ? 0 : conv_d1s_scratch_floats(d);
-  const size_t e3 = vol ? 0 : conv_d3s2_scratch_floats(d);
-  const size_t e = (e1 > e2 ? e1 : e2) > e3 ? (e1 > e2 ? e1 : e2) : e3;
-  const size_t abc = ab > c ? ab : c;
-  return abc > e ? abc : e;
-}
+// the last row of the selection (conv_dispatch.hip): takes whatever no other family took
+bool conv_direct_supported(const ddpm_conv_desc &) { return true; }
 
-// mirrors conv_dispatch: which kernel takes d, and whether its epilogue writes desc.stats_out
-int conv_stats_parts(const ddpm_conv_desc &d) {
-  const bool is3d = d.dims == 3 && d.ksize != 1;
-  if (is3d || d.ksize != 3 || d.Di > 1 || d.Do > 1 || linear_skinny_supported(d)) return 0;
-  if (conv_d3s_supported(d) || conv_d3s2_supported(d)) return conv_d3s_stats_parts(d);  // (from its reduce pass)
-  if (conv_wino44h_supported(d)) return conv_wino44h_stats_parts(d);
-  if (conv_wino44_supported(d)) return 0;
-  if (conv_wino_supported(d)) return conv_wino_stats_parts(d);  // (the Upsample form only)
-  if (d.mode == DDPM_CONV_STRIDE2 && conv_s2h_supported(d)) return conv_s2h_stats_parts(d);  // Downsample
+// slices of desc.stats_out launch_conv_direct's kernels write: conv_in's small-cin kernel only (the small-cout kernel goes first)
+int conv_direct_stats_parts(const ddpm_conv_desc &d) {
   int TH, RS, PS;
-  if (d.mode == DDPM_CONV_NORMAL && !conv_mfma_supported(d) && !smallco_supported(d, TH, RS, PS))
-    return smallci_stats_parts(d);  // conv_in (launch_conv_direct)
-  return 0;
-}
-
-int conv_dispatch(const ddpm_conv_desc &d, hipStream_t s) {
-  DDPM_CHECK_ARG(d.in1 && d.out && d.B > 0 && d.Cout > 0 && d.C1 > 0, "conv: null tensor or empty shape");
-  DDPM_CHECK_ARG(d.C2 == 0 || d.in2, "conv: C2 > 0 but in2 is NULL");
-  DDPM_CHECK_ARG((d.gscale == nullptr) == (d.gshift == nullptr), "conv: gscale/gshift must come together");
-  if (d.mode == DDPM_CONV_NORMAL)
-    DDPM_CHECK_ARG(d.Hi == d.Ho && d.Wi == d.Wo, "conv: normal mode needs Hi == Ho, Wi == Wo");
-  if (d.mode == DDPM_CONV_UPSAMPLE2)
-    DDPM_CHECK_ARG(d.Ho == 2 * d.Hi && d.Wo == 2 * d.Wi && d.ksize == 3, "conv: upsample needs Ho == 2 Hi, k == 3");
-  if (d.mode == DDPM_CONV_STRIDE2 && d.ksize == 3)
-    DDPM_CHECK_ARG(d.Ho == (d.Hi + 1) / 2 && d.Wo == (d.Wi + 1) / 2, "conv: stride-2 k3 needs Ho == ceil(Hi / 2)");
-  if (d.mode == DDPM_CONV_STRIDE2 && d.ksize == 4)
-    DDPM_CHECK_ARG(d.Ho == d.Hi / 2 && d.Wo == d.Wi / 2 && d.Ho > 0 && d.Wo > 0, "conv: stride-2 k4 needs Ho == Hi / 2");
-  DDPM_CHECK_ARG(d.mode != DDPM_CONV_STRIDE2 || d.ksize == 3 || d.ksize == 4, "conv: stride-2 needs k == 3 or 4");
-  const bool is3d = d.dims == 3 && d.ksize != 1;
-  if (is3d || d.mode == DDPM_CONV_TRANSPOSE2 || d.ksize == 4) {
-    // 3-D convolutions, k4 s2 and ConvTranspose only exist on the MFMA kernel (no generic fallback)
-    const int Di = d.Di > 1 ? d.Di : 1, Do = d.Do > 1 ? d.Do : 1;
-    if (is3d && d.mode == DDPM_CONV_NORMAL) DDPM_CHECK_ARG(Di == Do, "conv3d: normal mode needs Di == Do");
-    if (is3d && d.mode == DDPM_CONV_UPSAMPLE2) DDPM_CHECK_ARG(Do == 2 * Di, "conv3d: upsample needs Do == 2 Di");
-    if (is3d && d.mode == DDPM_CONV_STRIDE2)
-      DDPM_CHECK_ARG(Do == (d.ksize == 3 ? (Di + 1) / 2 : Di / 2) && Do > 0, "conv3d: stride-2 output depth");
-    if (is3d && conv_wino44h_supported(d)) return launch_conv_wino44h(d, s);         // VQ-VAE residual units, split-f16
-    if (is3d && conv_wino44_supported(d)) return launch_conv_wino44(d, s);
-    if (is3d && d.w_wino && conv_wino_supported(d)) return launch_conv_wino(d, s);
-    DDPM_CHECK_ARG(conv_mfma_supported(d),
-                   "conv: 3-D / k4 / transposed convolutions need an MFMA tiling (Cin %% 4 (8), Cout %% 128, packed weights)");
-    return launch_conv_mfma(d, s);
-  }
-  DDPM_CHECK_ARG(d.Di <= 1 && d.Do <= 1, "conv: Di / Do > 1 needs dims == 3");
-  if (linear_skinny_supported(d)) return launch_linear_skinny(d, s);  // Linear over <= 1024 rows: latency, not FLOPs
-  if (conv_d3s_supported(d)) return launch_conv_d3s(d, s);          // small launches: one-shot direct 3x3, split-f16 (round 4)
-  if (conv_wino44h_supported(d)) return launch_conv_wino44h(d, s);  // F(4x4) with split-f16 position GEMMs
-  if (conv_wino44_supported(d)) return launch_conv_wino44(d, s);
-  if (conv_wino_supported(d)) return launch_conv_wino(d, s);
-  if (conv_d3s2_supported(d)) return launch_conv_d3s2(d, s);  // Downsample of small launches: one-shot, split-f16 (round 4)
-  if (conv_s2h_supported(d)) return launch_conv_s2h(d, s);  // Downsample: direct 3x3 stride 2 on the f16 MFMA, split-f16 operands
-  if (conv_d1s_supported(d)) return launch_conv_d1s(d, s);  // small launches: one-shot 1x1, split-f16 (round 4)
-  if (conv1x1_dma_supported(d) && conv_mfma_supported(d)) return launch_conv1x1_dma(d, s);
-  if (conv_mfma_supported(d)) return launch_conv_mfma(d, s);
-  return launch_conv_direct(d, s);
+  return d.mode == DDPM_CONV_NORMAL && !smallco_supported(d, TH, RS, PS) ? smallci_stats_parts(d) : 0;
 }
 
 }  // namespace ddpm
-
-// Would ddpm_conv_f32 run this stride-1 3x3 descriptor on the split-f16 F(4x4) kernel if it were given w_wino44h?  (A caller that
-// re-packs weights every step -- the training step -- packs the F(2x2) fallback form only when the answer is no.)
-extern "C" int ddpm_conv_takes_wino44h(const ddpm_conv_desc *dp) {
-  if (!dp) return 0;
-  ddpm_conv_desc d = *dp;
-  if (d.dims == 3 || d.ksize != 3) return 0;
-  if (!d.w_wino44h) d.w_wino44h = reinterpret_cast<const uint16_t *>(uintptr_t(64));  // (only tested for non-NULL)
-  if (!d.scratch) {  // (a launch split over channel slices needs scratch: the caller will size it with ddpm_conv_scratch_floats)
-    d.scratch = reinterpret_cast<float *>(uintptr_t(64));
-    d.scratch_floats = ~size_t(0);
-  }
-  if (ddpm::linear_skinny_supported(d) || (d.w_d3h && ddpm::conv_d3s_supported(d))) return 0;
-  return ddpm::conv_wino44h_supported(d) ? 1 : 0;
-}
-

@@ -199,9 +199,8 @@ int conv_wino_stats_parts(const ddpm_conv_desc &d) {
 }
 
 bool conv_wino_supported(const ddpm_conv_desc &d) {
-  static const bool enabled = !(getenv("DDPM_CONV_WINOGRAD") && atoi(getenv("DDPM_CONV_WINOGRAD")) == 0);
   WinoGeom g;
-  return enabled && d.w_wino != nullptr && !d.force_direct && wino_geom(d, g);
+  return sw().conv_winograd && d.w_wino != nullptr && !d.force_direct && wino_geom(d, g);
 }
 
 // D3: the 3-D form (images = (n, d) slices, chunk stream = (depth tap, channel chunk)); a template parameter so that

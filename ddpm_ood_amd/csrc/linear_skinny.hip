@@ -22,8 +22,7 @@ typedef float v4fs __attribute__((ext_vector_type(4)));
 constexpr int kSkinnyMaxRows = 1024;
 
 bool linear_skinny_supported(const ddpm_conv_desc &d) {
-  static const bool enabled = !(getenv("DDPM_LINEAR_SKINNY") && atoi(getenv("DDPM_LINEAR_SKINNY")) == 0);
-  if (!enabled || d.ksize != 1 || d.mode != DDPM_CONV_NORMAL || !d.w_raw || d.force_direct) return false;
+  if (!sw().linear_skinny || d.ksize != 1 || d.mode != DDPM_CONV_NORMAL || !d.w_raw || d.force_direct) return false;
   if (d.Hi != 1 || d.Wi != 1 || d.Ho != 1 || d.Wo != 1 || d.Di > 1 || d.Do > 1) return false;
   if (d.C2 || d.gscale || d.residual || d.chan_add || d.out_act != DDPM_ACT_NONE) return false;
   if (d.act != DDPM_ACT_NONE && d.act != DDPM_ACT_SILU) return false;

@@ -174,6 +174,13 @@ int ddpm_pack_conv1x1_h_weight(const float *w_raw, uint16_t *dst, int Cout, int 
 /* Slices per (image, channel) of the statistics ddpm_conv_f32 writes to d->stats_out for this descriptor (1 .. 8), or 0
  * when the kernel it dispatches to does not emit them (the caller then runs ddpm_gn_scale_shift_f32 on the tensor).  */
 int ddpm_conv_stats_parts(const ddpm_conv_desc *d);
+/* Host-only: the name of the kernel family ddpm_conv_f32 would run this descriptor on ("wino44h", "d3s", "s2h", "mfma", "direct",
+ * ...: the rows of the selection table in csrc/conv_dispatch.hip, which ddpm_conv_stats_parts, ddpm_conv_scratch_floats and
+ * ddpm_conv_takes_wino44h answer from as well), or "" for a NULL or invalid descriptor (ddpm_last_error says why).  Pointers
+ * are only looked at for NULL-ness and alignment.  ddpm_conv_kernel_scratch_floats: the scratch that family alone would use
+ * (<= ddpm_conv_scratch_floats, which is sized before the scratch is attached and so covers every family that could take it).  */
+const char *ddpm_conv_kernel_name(const ddpm_conv_desc *desc);
+size_t ddpm_conv_kernel_scratch_floats(const ddpm_conv_desc *desc);
 
 /* Number of floats of the packed form of a [Cout, Cin, k, k] weight (0 if unpackable). */
 size_t ddpm_packed_conv_weight_floats(int Cout, int Cin, int ksize);
