@@ -179,6 +179,10 @@ SIGNATURES = {
                                        C.c_int, C.c_void_p]),
     "ddpm_conv3d_wgrad_scratch_floats": (C.c_size_t, [C.c_int] * 10),
     "ddpm_conv3d_wgrad_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 10 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ddpm_conv_k4s2_wgrad_scratch_floats": (C.c_size_t, [C.c_int] * 7),
+    "ddpm_conv_k4s2_wgrad_split": (C.c_int, [C.c_int] * 7),
+    "ddpm_conv_k4s2_wgrad_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "ddpm_relu_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ddpm_resample3_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ddpm_conv_weight_rot180t_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ddpm_gn_stats_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),

@@ -871,6 +871,144 @@ __global__ __launch_bounds__(256) void conv_wgrad_generic_kernel(const float *__
   }
 }
 
+// ------------------------------------------------------------------------------------------------ k4 s2 p1 weight gradient
+// dW[co, ci, ky, kx] = sum over (image, output pixel) of dY[co, (yo, xo)] A[ci, (2 yo + ky - 1, 2 xo + kx - 1)], A outside the image
+// read as 0: the weight gradient of the VQ-VAE's down-convolutions and -- with (A, dY) := (dY, X) -- of its transposed
+// convolutions.  The contraction and the tiling of conv3x3_wgrad_kernel: 64 couts x 64 cins per workgroup, the pixel stream split
+// over workgroups, partial sums to part[slice][16 taps][cout][cin].  Sixteen 32x32 accumulator tiles per wave do not fit beside
+// the staging registers, so a workgroup has eight waves: waves 0-3 hold the taps of kernel rows 0 and 1, waves 4-7 those of rows 2
+// and 3, each eight tiles (128 accumulator registers, two waves per SIMD).  3-D: one launch per depth tap kd, image = (batch item,
+// output slice zo), input slice zi = 2 zo + kd - 1 (outside the volume: nothing).  Global addressing is 64-bit throughout.
+struct WgradK4P {
+  const float *a;   // [B, Cin, Di, Hi, Wi]
+  const float *dy;  // [B, Cout, Do, Ho, Wo]
+  float *part;      // [S][16][Cout][Cin]
+  int B, Cin, Cout, Hi, Wi, Ho, Wo, Di, Do, kd;
+  long long a_cs, dy_cs;  // channel strides in floats
+  int R, tiles_per_img, T, S;  // output rows per pixel tile; T pixel tiles walked by S workgroups per (cout, cin) block
+  int AR, AW, ACS, DCS;        // input tile: rows (2 R + 2), row length (Wi + 2), channel stride (odd); dY tile channel stride (odd)
+};
+
+__global__ __launch_bounds__(512) void conv_k4s2_wgrad_kernel(const WgradK4P p) {
+  extern __shared__ float smem[];
+  float *Ds = smem;                   // [64 co][DCS]
+  float *As = smem + kWT * p.DCS;     // [64 ci][ACS]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, lhi = lane >> 5;
+  const int cob = blockIdx.x * kWT, cib = blockIdx.y * kWT, sp = blockIdx.z;
+  const int quad = wave & 3, kh = wave >> 2;  // kh: kernel rows 2 kh and 2 kh + 1
+  const int wco = (quad >> 1) * 32, wci = (quad & 1) * 32;
+  const int PT = p.R * p.Wo;  // pixels per tile (Wo is even: a pixel pair stays inside a row)
+  f32x16 acc[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+  const size_t hw_i = (size_t)p.Hi * p.Wi, hw_o = (size_t)p.Ho * p.Wo;
+  const int atile = p.AR * p.AW;
+  for (int tile = sp; tile < p.T; tile += p.S) {
+    const int sl = tile / p.tiles_per_img, rb = tile - sl * p.tiles_per_img;
+    const int b = sl / p.Do, zo = sl - b * p.Do, zi = 2 * zo + p.kd - 1;
+    if (zi < 0 || zi >= p.Di) continue;  // (uniform over the workgroup)
+    const int yo0 = rb * p.R;
+    const int rows = min(p.R, p.Ho - yo0);  // (a ragged last tile: the missing rows are zero)
+    // ---- dY tile: 64 couts x PT pixels (contiguous in memory)
+    const float *dyb = p.dy + ((size_t)b * p.Cout + cob) * p.dy_cs + (size_t)zo * hw_o + (size_t)yo0 * p.Wo;
+    for (int e = tid; e < kWT * PT; e += 512) {
+      const int c = e / PT, px = e - c * PT;
+      Ds[c * p.DCS + px] = px < rows * p.Wo ? dyb[(size_t)c * p.dy_cs + px] : 0.f;
+    }
+    // ---- input tile: 64 cins x AR rows x AW columns, zero halo; tile row r holds input row 2 yo0 - 1 + r, column c input column c - 1
+    const float *ab = p.a + ((size_t)b * p.Cin + cib) * p.a_cs + (size_t)zi * hw_i;
+    const int yi0 = 2 * yo0 - 1;
+    for (int e = tid; e < kWT * atile; e += 512) {
+      const int c = e / atile, rem = e - c * atile;
+      const int r = rem / p.AW, col = rem - r * p.AW;
+      const int yi = yi0 + r, xi = col - 1;
+      float v = 0.f;
+      if (yi >= 0 && yi < p.Hi && xi >= 0 && xi < p.Wi) v = ab[(size_t)c * p.a_cs + (size_t)yi * p.Wi + xi];
+      As[c * p.ACS + rem] = v;
+    }
+    __syncthreads();
+    const float *dsw = Ds + (wco + l31) * p.DCS + lhi;
+    const float *asw = As + (wci + l31) * p.ACS + 2 * kh * p.AW + 2 * lhi;
+    for (int yo = 0; yo < p.R; ++yo) {
+      const float *dr = dsw + yo * p.Wo;
+      const float *ar = asw + 2 * yo * p.AW;  // tap (ky, kx) of pixel (yo, xo): tile row 2 yo + ky, column 2 xo + kx
+      for (int xo = 0; xo < p.Wo; xo += 2) {
+        const float d = dr[xo];
+        const float *ap = ar + 2 * xo;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          const float bv = ap[(t >> 2) * p.AW + (t & 3)];
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(d, bv, acc[t], 0, 0, 0);
+        }
+      }
+    }
+    __syncthreads();
+  }
+  // partial sums: part[sp][tap][co][ci] (ci fastest: coalesced), tap = 4 ky + kx = 8 kh + t
+  float *out = p.part + (size_t)sp * 16 * p.Cout * p.Cin;
+#pragma unroll
+  for (int t = 0; t < 8; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int co = cob + wco + 8 * (i >> 2) + 4 * lhi + (i & 3);
+      out[((size_t)(8 * kh + t) * p.Cout + co) * p.Cin + cib + wci + l31] = acc[t][i];
+    }
+}
+
+// Any (Cout, Cin) and any even extents: one workgroup per (cout, cin) pair and slice of the (image, output position) stream, the 16
+// (2-D) or 64 (3-D) taps of the pair in registers, summed in a fixed order.  The 1-channel first / last layers of the VQ-VAE have
+// 256 pairs and 64^3 / 8 positions per image: the stream is cut into gridDim.y slices (partial sums to part[slice][tap][cout][cin]
+// for wgrad_reduce_kernel), not one thread per output.
+template <int DIMS>
+__global__ __launch_bounds__(256) void conv_k4s2_wgrad_generic_kernel(const float *__restrict__ a, const float *__restrict__ dy,
+                                                                      float *__restrict__ dw, float *__restrict__ part, int B, int Cin,
+                                                                      int Cout, int Di, int Hi, int Wi, long long chunk) {
+  constexpr int KD = DIMS == 3 ? 4 : 1, TAPS = 16 * KD;
+  __shared__ float red[4];
+  const int co = blockIdx.x / Cin, ci = blockIdx.x - co * Cin;
+  const int Do = DIMS == 3 ? Di / 2 : 1, Ho = Hi / 2, Wo = Wi / 2;
+  const long long npos = (long long)Do * Ho * Wo, total = (long long)B * npos;
+  const long long e0 = (long long)blockIdx.y * chunk, e1 = e0 + chunk < total ? e0 + chunk : total;
+  const size_t a_cs = (size_t)(DIMS == 3 ? Di : 1) * Hi * Wi;
+  float s[TAPS];
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t) s[t] = 0.f;
+  for (long long e = e0 + threadIdx.x; e < e1; e += 256) {
+    const long long b = e / npos, pos = e - b * npos;
+    const int zo = (int)(pos / ((long long)Ho * Wo)), rem = (int)(pos - (long long)zo * Ho * Wo);
+    const int yo = rem / Wo, xo = rem - yo * Wo;
+    const float g = dy[((size_t)b * Cout + co) * (size_t)npos + (size_t)pos];
+    const float *ap = a + ((size_t)b * Cin + ci) * a_cs;
+#pragma unroll
+    for (int kd = 0; kd < KD; ++kd) {
+      const int zi = DIMS == 3 ? 2 * zo + kd - 1 : 0;
+      const bool zok = DIMS == 3 ? (zi >= 0 && zi < Di) : true;
+#pragma unroll
+      for (int ky = 0; ky < 4; ++ky) {
+        const int yi = 2 * yo + ky - 1;
+        const bool yok = zok && yi >= 0 && yi < Hi;
+#pragma unroll
+        for (int kx = 0; kx < 4; ++kx) {
+          const int xi = 2 * xo + kx - 1;
+          if (yok && xi >= 0 && xi < Wi)
+            s[(kd * 4 + ky) * 4 + kx] = __builtin_fmaf(g, ap[((size_t)zi * Hi + yi) * Wi + xi], s[(kd * 4 + ky) * 4 + kx]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t) {
+    const float v = block_sum_256(s[t], red);
+    if (threadIdx.x == 0) {
+      if (gridDim.y > 1) part[(((size_t)blockIdx.y * TAPS + t) * Cout + co) * Cin + ci] = v;
+      else dw[((size_t)co * Cin + ci) * TAPS + t] = v;
+    }
+  }
+}
+
 }  // namespace
 
 }  // namespace ddpm
@@ -1209,6 +1347,135 @@ extern "C" int ddpm_conv3d_wgrad_f32(const float *a, const float *dy, float *dw,
     p.kd = kd;
     wgrad_launch(p, aligned, s);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p.part, dw, p.S, Cout, Cin, 9, 27, 9 * kd);
+  }
+  DDPM_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ k4 s2 p1 weight gradient
+namespace {
+bool wgrad_k4_plan(int B, int Cin, int Cout, int Di, int Hi, int Wi, int dims, WgradK4P &p) {
+  if (Cin % kWT || Cout % kWT) return false;
+  const int Do = dims == 3 ? Di / 2 : 1, Ho = Hi / 2, Wo = Wi / 2;
+  if (Wo > 64 || (Wo & 1)) return false;  // pixel pairs stay inside a row
+  p.B = B; p.Cin = Cin; p.Cout = Cout; p.Hi = Hi; p.Wi = Wi; p.Ho = Ho; p.Wo = Wo;
+  p.Di = dims == 3 ? Di : 1; p.Do = Do; p.kd = 1;
+  p.a_cs = (long long)p.Di * Hi * Wi; p.dy_cs = (long long)Do * Ho * Wo;
+  // output rows per pixel tile: 64 pixels where the tiles fit 64 KB of LDS, else fewer rows
+  p.R = 64 / Wo < Ho ? 64 / Wo : Ho;
+  if (p.R < 1) p.R = 1;
+  for (;; p.R = (p.R + 1) / 2) {
+    p.AR = 2 * p.R + 2;
+    p.AW = Wi + 2;
+    p.ACS = p.AR * p.AW;
+    if (!(p.ACS & 1)) p.ACS += 1;
+    p.DCS = p.R * Wo + 1;
+    const size_t lds = (size_t)kWT * (p.ACS + p.DCS) * sizeof(float);
+    if (lds <= 64 * 1024) break;
+    if (p.R == 1) {
+      if (lds > 150 * 1024) return false;
+      break;
+    }
+  }
+  p.tiles_per_img = (Ho + p.R - 1) / p.R;
+  const long long T = (long long)B * Do * p.tiles_per_img;
+  if (T > 0x7fffffffLL) return false;
+  p.T = (int)T;
+  const int blocks = (Cout / kWT) * (Cin / kWT);
+  int S = device_cus() / blocks;  // one round of one workgroup per CU
+  if (S > p.T / 4) S = p.T / 4;   // at least four pixel tiles per slice
+  if (S < 1) S = 1;
+  p.S = S;
+  return true;
+}
+
+// slices of the generic form's (image, output position) stream: about four workgroups per CU, at least 2 048 positions per slice
+int wgrad_k4_generic_slices(int B, int Cin, int Cout, int Di, int Hi, int Wi, int dims, long long &chunk) {
+  const long long total = (long long)B * (dims == 3 ? Di / 2 : 1) * (Hi / 2) * (Wi / 2);
+  const long long pairs = (long long)Cout * Cin, want = 4LL * device_cus();
+  long long S = pairs >= want ? 1 : (want + pairs - 1) / pairs;
+  if (S > total / 2048) S = total / 2048;
+  if (S > 65535) S = 65535;
+  if (S < 1) S = 1;
+  chunk = (total + S - 1) / S;
+  S = (total + chunk - 1) / chunk;
+  return (int)S;
+}
+
+bool wgrad_k4_args_ok(int B, int Cin, int Cout, int Di, int Hi, int Wi, int dims) {
+  return B > 0 && Cin > 0 && Cout > 0 && (dims == 2 || dims == 3) && Hi >= 2 && Wi >= 2 && !(Hi & 1) && !(Wi & 1) &&
+         (dims == 2 || (Di >= 2 && !(Di & 1)));
+}
+}  // namespace
+
+extern "C" int ddpm_conv_k4s2_wgrad_split(int B, int Cin, int Cout, int Di, int Hi, int Wi, int dims) {
+  WgradK4P p;
+  if (!wgrad_k4_args_ok(B, Cin, Cout, Di, Hi, Wi, dims) || !wgrad_k4_plan(B, Cin, Cout, Di, Hi, Wi, dims, p)) return 0;
+  return p.S;
+}
+
+extern "C" size_t ddpm_conv_k4s2_wgrad_scratch_floats(int B, int Cin, int Cout, int Di, int Hi, int Wi, int dims) {
+  if (!wgrad_k4_args_ok(B, Cin, Cout, Di, Hi, Wi, dims)) return 0;
+  WgradK4P p;
+  size_t need = 0;
+  if (wgrad_k4_plan(B, Cin, Cout, Di, Hi, Wi, dims, p)) need = (size_t)p.S * 16 * Cout * Cin;
+  long long chunk;
+  const int S = wgrad_k4_generic_slices(B, Cin, Cout, Di, Hi, Wi, dims, chunk);
+  if (S > 1) need = std::max(need, (size_t)S * (dims == 3 ? 64 : 16) * Cout * Cin);
+  return need;
+}
+
+extern "C" int ddpm_conv_k4s2_wgrad_f32(const float *a, const float *dy, float *dw, int B, int Cin, int Cout, int Di, int Hi, int Wi,
+                                        int dims, float *scratch, size_t scratch_floats, int force_generic, ddpm_stream_t stream) {
+  DDPM_CHECK_ARG(a && dy && dw, "conv_k4s2_wgrad: null operand");
+  DDPM_CHECK_ARG(wgrad_k4_args_ok(B, Cin, Cout, Di, Hi, Wi, dims),
+                 "conv_k4s2_wgrad: dims %d, B %d, %d -> %d channels, extents %d x %d x %d (dims 2 or 3, every extent even and >= 2)", dims, B,
+                 Cin, Cout, Di, Hi, Wi);
+  hipStream_t s = as_stream(stream);
+  const int KD = dims == 3 ? 4 : 1, taps = 16 * KD;
+  const double M = (double)B * (dims == 3 ? Di / 2 : 1) * (Hi / 2) * (Wi / 2);
+  const double flops = 2.0 * M * Cout * Cin * taps;
+  const double bytes = 4.0 * (8.0 * M * Cin + M * Cout + (double)taps * Cout * Cin);
+  WgradK4P p;
+  if (!force_generic && wgrad_k4_plan(B, Cin, Cout, Di, Hi, Wi, dims, p)) {
+    DDPM_CHECK_ARG(scratch && scratch_floats >= (size_t)p.S * 16 * Cout * Cin,
+                   "conv_k4s2_wgrad: the matrix-pipe form needs the scratch of ddpm_conv_k4s2_wgrad_scratch_floats");
+    p.a = a; p.dy = dy; p.part = scratch;
+    static bool attr = false;
+    if (!attr) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_k4s2_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024);
+      attr = true;
+    }
+    ProfScope prof(s, dims == 3 ? "train_conv3d_k4s2_wgrad" : "train_conv_k4s2_wgrad", flops, bytes);
+    const dim3 grid(Cout / kWT, Cin / kWT, p.S);
+    const size_t lds = (size_t)kWT * (p.ACS + p.DCS) * sizeof(float);
+    const size_t n = (size_t)Cout * Cin * 16;
+    for (int kd = 0; kd < KD; ++kd) {  // one depth tap per launch (2-D: the one launch, kd = 1 reads "slice" 2 * 0 + 1 - 1 = 0)
+      p.kd = dims == 3 ? kd : 1;
+      hipLaunchKernelGGL(conv_k4s2_wgrad_kernel, grid, dim3(512), lds, s, p);
+      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p.part, dw, p.S, Cout, Cin, 16, taps,
+                         16 * kd);
+    }
+    DDPM_CHECK_LAUNCH();
+    return 0;
+  }
+  DDPM_CHECK_ARG((long long)Cout * Cin <= 0x7fffffffLL, "conv_k4s2_wgrad: too many (cout, cin) pairs for the generic kernel");
+  long long chunk;
+  int S = wgrad_k4_generic_slices(B, Cin, Cout, Di, Hi, Wi, dims, chunk);
+  if (S > 1 && (!scratch || scratch_floats < (size_t)S * taps * Cout * Cin)) {  // no room for slabs: one slice
+    S = 1;
+    chunk = (long long)M;
+  }
+  ProfScope prof(s, "train_conv_k4s2_wgrad_generic", flops, bytes);
+  const dim3 grid(Cout * Cin, S);
+  if (dims == 3)
+    hipLaunchKernelGGL(conv_k4s2_wgrad_generic_kernel<3>, grid, dim3(256), 0, s, a, dy, dw, scratch, B, Cin, Cout, Di, Hi, Wi, chunk);
+  else
+    hipLaunchKernelGGL(conv_k4s2_wgrad_generic_kernel<2>, grid, dim3(256), 0, s, a, dy, dw, scratch, B, Cin, Cout, 1, Hi, Wi, chunk);
+  if (S > 1) {
+    const size_t n = (size_t)Cout * Cin * taps;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scratch, dw, S, Cout, Cin, taps, taps, 0);
   }
   DDPM_CHECK_LAUNCH();
   return 0;

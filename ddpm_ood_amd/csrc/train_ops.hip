@@ -459,6 +459,11 @@ __global__ void silu_bwd_kernel(const float *__restrict__ x, const float *__rest
   const float v = x[i], sg = sigmoid_f(v);
   dx[i] = dy[i] * sg * (1.0f + v * (1.0f - sg));
 }
+// dx = dy where the saved post-ReLU output is positive, 0 elsewhere (a tie at 0 carries no gradient)
+__global__ void relu_bwd_kernel(const float *__restrict__ y, const float *__restrict__ dy, float *__restrict__ dx, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dx[i] = y[i] > 0.f ? dy[i] : 0.f;
+}
 __global__ void axpby_kernel(const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ out, float alpha, float beta,
                              int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -777,6 +782,15 @@ extern "C" int ddpm_silu_backward_f32(const float *x, const float *dy, float *dx
   DDPM_CHECK_ARG(x && dy && dx && n > 0, "silu_backward: bad arguments");
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(silu_bwd_kernel, dim3(blocks_for(n)), dim3(256), 0, s, x, dy, dx, n);
+  DDPM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ddpm_relu_backward_f32(const float *y, const float *dy, float *dx, int64_t n, ddpm_stream_t stream) {
+  DDPM_CHECK_ARG(y && dy && dx && n > 0, "relu_backward: bad arguments");
+  hipStream_t s = as_stream(stream);
+  ProfScope prof(s, "train_relu_backward", 0.0, 12.0 * n);
+  hipLaunchKernelGGL(relu_bwd_kernel, dim3(blocks_for(n)), dim3(256), 0, s, y, dy, dx, n);
   DDPM_CHECK_LAUNCH();
   return 0;
 }

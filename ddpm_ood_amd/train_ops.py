@@ -94,6 +94,48 @@ def conv3d_wgrad(a, dy, stride: int = 1, out=None):
     return out
 
 
+def _k4s2_geometry(a, dy):
+    a, dy = require_device_f32(a, "a"), require_device_f32(dy, "dy")
+    dims = a.ndim - 2
+    if dims not in (2, 3) or dy.ndim != a.ndim or a.shape[0] != dy.shape[0] or \
+            any(e % 2 or o != e // 2 for e, o in zip(a.shape[2:], dy.shape[2:])):
+        raise ValueError(f"conv_k4s2_wgrad: a {tuple(a.shape)} / dy {tuple(dy.shape)}: wants a [B, Cin, (D,) H, W] with even extents "
+                         "and dy [B, Cout, (D / 2,) H / 2, W / 2]")
+    Di, Hi, Wi = ((1,) + tuple(a.shape[2:])) if dims == 2 else tuple(a.shape[2:])
+    return a, dy, (a.shape[0], a.shape[1], dy.shape[1], Di, Hi, Wi, dims)
+
+
+def conv_k4s2_wgrad_split(a, dy) -> int:
+    """Workgroups that share the (image, output position) stream of one (cout, cin) tile in the matrix-pipe form of
+    ``conv_k4s2_wgrad`` for these operands (0: the shape has no such tiling and takes the generic form)."""
+    return int(_lib.load().ddpm_conv_k4s2_wgrad_split(*_k4s2_geometry(a, dy)[2]))
+
+
+def conv_k4s2_wgrad(a, dy, out=None, force_generic: bool = False):
+    """dw[Cout, Cin, 4, 4(, 4)] of F.conv{2,3}d(a, w, stride=2, padding=1) given dy.  The weight gradient of the TRANSPOSED
+    convolution y = F.conv_transpose{2,3}d(x, w[Cin, Cout, 4, ...], stride=2, padding=1) is conv_k4s2_wgrad(a=dy, dy=x), already in
+    torch's [Cin, Cout, 4, ...] layout."""
+    lib = _lib.load()
+    a, dy, geom = _k4s2_geometry(a, dy)
+    if out is None:
+        out = _empty((geom[2], geom[1]) + (4,) * geom[6], a)
+    need = lib.ddpm_conv_k4s2_wgrad_scratch_floats(*geom)
+    scratch = _empty((need,), a) if need else None
+    check(lib.ddpm_conv_k4s2_wgrad_f32(ptr(a), ptr(dy), ptr(out), *geom, ptr(scratch), need, int(force_generic), stream_ptr()),
+          "conv_k4s2_wgrad")
+    return out
+
+
+def relu_backward(y, dy):
+    """dx = dy * (y > 0) from the saved post-ReLU output (a tie at 0 carries no gradient)."""
+    y, dy = require_device_f32(y, "y"), require_device_f32(dy, "dy")
+    if y.shape != dy.shape:
+        raise ValueError(f"relu_backward: y {tuple(y.shape)} and dy {tuple(dy.shape)} differ")
+    dx = torch.empty_like(dy)
+    check(_lib.load().ddpm_relu_backward_f32(ptr(y), ptr(dy), ptr(dx), y.numel(), stream_ptr()), "relu_backward")
+    return dx
+
+
 def gn_stats(x, groups: int, eps: float):
     x = require_device_f32(x, "x")
     B, Cc = x.shape[:2]

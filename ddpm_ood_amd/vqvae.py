@@ -178,21 +178,28 @@ class _ResidualUnit(nn.Module):
                             ops.pack_wino44h_3d_weight(w1.detach()), ops.pack_wino44h_3d_weight(w2.detach()))
         return self._packed[1:]
 
-    def forward(self, x):
-        w1, w2 = self.conv1.conv.weight, self.conv2.conv.weight
-        if x.is_cuda and x.ndim == 5 and ops.conv3d_supported(w1) and ops.conv3d_supported(w2):
+    def _mfma3d(self, x):
+        return x.is_cuda and x.ndim == 5 and ops.conv3d_supported(self.conv1.conv.weight) and \
+            ops.conv3d_supported(self.conv2.conv.weight)
+
+    def head(self, x):
+        """relu(conv1(x)) on a float32 contiguous x (the first half of ``forward``; the native training step runs the two halves as
+        two autograd functions over the same kernels)."""
+        if self._mfma3d(x):
             # 95 % of the decoder's FLOPs: both 3x3x3 convolutions on the fp32 MFMA pipe, one launch each (Winograd
             # per depth tap -- F(4x4) from 32^3 up, F(2x2) at 16^3; the direct kernel below that), ReLU /
             # residual fused into the epilogues
-            p1, p2, u1, u2, v1, v2, h1, h2 = self._hip_weights()
-            x = x.float().contiguous()
-            h = ops.conv3d(x, w1.detach(), self.conv1.conv.bias.detach(), out_act=ops.ACT_RELU, packed=p1, wino=u1,
-                           wino44=v1, wino44h=h1)
-            return ops.conv3d(h, w2.detach(), self.conv2.conv.bias.detach(), residual=x, out_act=ops.ACT_RELU,
+            p1, _p2, u1, _u2, v1, _v2, h1, _h2 = self._hip_weights()
+            return ops.conv3d(x, self.conv1.conv.weight.detach(), self.conv1.conv.bias.detach(), out_act=ops.ACT_RELU, packed=p1,
+                              wino=u1, wino44=v1, wino44h=h1)
+        return self.conv1(x)  # generic kernel (2-D layers with an MFMA tiling: the UNet's convolution), ReLU fused
+
+    def tail(self, h, x):
+        """relu(x + conv2(h)): the second half of ``forward``."""
+        if self._mfma3d(x):
+            _p1, p2, _u1, u2, _v1, v2, _h1, h2 = self._hip_weights()
+            return ops.conv3d(h, self.conv2.conv.weight.detach(), self.conv2.conv.bias.detach(), residual=x, out_act=ops.ACT_RELU,
                               packed=p2, wino=u2, wino44=v2, wino44h=h2)
-        _require_device(x)
-        x = x.float().contiguous()
-        h = self.conv1(x)  # generic kernel (2-D layers with an MFMA tiling: the UNet's convolution), ReLU fused
         c2 = self.conv2
         sd, k, s, dil, pad, opad = c2.geom
         if c2._hip_kind(h) == "conv2d":  # relu(x + conv2(h)): residual and ReLU in the MFMA kernel's epilogue
@@ -204,6 +211,12 @@ class _ResidualUnit(nn.Module):
                             residual=x, out_act=ops.ACT_RELU)
         return ops.convnd_generic(h, c2.conv.weight.detach(), c2.conv.bias.detach() if c2.conv.bias is not None else None,
                                   stride=s, padding=pad, residual=x, relu=True)
+
+    def forward(self, x):
+        if not self._mfma3d(x):
+            _require_device(x)
+        x = x.float().contiguous()
+        return self.tail(self.head(x), x)
 
 
 class _Stack(nn.Module):

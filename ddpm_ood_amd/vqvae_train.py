@@ -5,9 +5,11 @@ Adam at ``--vqvae_learning_rate``, epoch loop, five-key checkpoint dict, resume,
 ``--eval_freq``, ``--quick_test``).  What runs where:
   * the quantiser's training step -- nearest-code search, per-code counts and sums, EMA codebook update, commitment loss and
     its straight-through backward -- is HIP (``vq.hip``: ddpm_vq_train_{assign,update,backward}_f32) behind ``VQTrainFunction``;
-  * the encoder / decoder gradients go through PyTorch-ROCm autograd over ``encode_train`` / ``decode_train``: a differentiable
-    ATen forward that evaluates the SAME parameter holders the HIP engine of ``vqvae.VQVAE`` reads (how the UNet's training step
-    started before it went native; native k4-s2 / transposed weight-gradient kernels are the follow-up, DESIGN.md 8);
+  * the encoder / decoder gradients go by default through PyTorch-ROCm autograd over ``encode_train`` / ``decode_train``: a
+    differentiable ATen forward that evaluates the SAME parameter holders the HIP engine of ``vqvae.VQVAE`` reads.
+    ``DDPM_VQVAE_NATIVE=1`` runs them on the library instead (``vqvae_native.py``): forward on the eval path's
+    kernels, backward on the weight-gradient kernels (3x3 / 3x3x3 and k4 s2 p1) and the inference kernels as input-gradient
+    convolutions; ``last_stats["conv_gradients"]`` says which route a step took;
   * the optimised loss is L1 + quantisation (commitment) loss by default.  ``DDPM_VQVAE_LOSS_TERMS`` (a comma list drawn from
     ``perceptual``, ``spectral``; unknown names raise) adds the reference's 0.001 x LPIPS-AlexNet term and its Jukebox spectral
     term, forward and backward on HIP kernels (``loss_terms.py``); ``DDPM_LPIPS_WEIGHTS=<state_dict file>`` loads
@@ -34,7 +36,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import _lib, loss_terms, ops
+from . import _lib, loss_terms, ops, vqvae_native
 from .data import get_data_loader
 from .perceptual import LPIPS
 from .vqvae import VQVAE, _ResidualUnit
@@ -124,20 +126,31 @@ def _stack_train(stack, x):
     return x
 
 
+def native_conv_gradients() -> bool:
+    """DDPM_VQVAE_NATIVE=1: the encoder / decoder run forward on the eval path's HIP kernels and backward on the library's
+    weight- and input-gradient kernels (``vqvae_native``).  Unset or 0: the ATen route above.  Read per call."""
+    return os.environ.get("DDPM_VQVAE_NATIVE", "0") not in ("", "0")
+
+
 def _check_trainable(model):
     if getattr(model, "dropout", 0.0):
         raise NotImplementedError(f"vqvae_dropout = {model.dropout}: dropout is not built (the reference trains with 0.0)")
 
 
 def encode_train(model: VQVAE, images: torch.Tensor) -> torch.Tensor:
-    """``model.encode`` with ATen ops and autograd over the model's own parameters (any device, 2-D or 3-D)."""
+    """``model.encode`` with autograd over the model's own parameters: ATen ops (any device, 2-D or 3-D), or -- DDPM_VQVAE_NATIVE=1 --
+    the eval path's HIP kernels with a native backward (device only)."""
     _check_trainable(model)
+    if native_conv_gradients():
+        return vqvae_native.stack_train(model.encoder, images)
     return _stack_train(model.encoder, images.float())
 
 
 def decode_train(model: VQVAE, quantizations: torch.Tensor) -> torch.Tensor:
-    """``model.decode`` with ATen ops and autograd over the model's own parameters (any device, 2-D or 3-D)."""
+    """``model.decode`` with autograd over the model's own parameters: ATen ops, or the HIP kernels (see ``encode_train``)."""
     _check_trainable(model)
+    if native_conv_gradients():
+        return vqvae_native.stack_train(model.decoder, quantizations)
     return _stack_train(model.decoder, quantizations.float())
 
 
@@ -210,6 +223,7 @@ class VQVAETrainer:
         self.loss_terms = loss_terms.parse_terms(os.environ.get("DDPM_VQVAE_LOSS_TERMS"))
         missing = [m for m, t in zip(MISSING_LOSS_TERMS, _TERM_OF_MISSING) if t not in self.loss_terms]
         self.last_stats = {"missing_loss_terms": missing, "optimised_loss": _loss_text("l1 + quantization", self.loss_terms)}
+        self.last_stats["conv_gradients"] = "native" if native_conv_gradients() else "aten"
         self.last_terms = {}
         if "missing_terms" not in _WARNED:
             _WARNED.add("missing_terms")
@@ -332,6 +346,7 @@ class VQVAETrainer:
         """One optimisation step on a device batch -> (total loss, L1, quantisation loss) as device scalars; the values of the
         enabled extra terms (unweighted) go to ``self.last_terms``."""
         self.optimizer.zero_grad(set_to_none=True)
+        self.last_stats["conv_gradients"] = "native" if native_conv_gradients() else "aten"
         reconstruction, quantization_loss = vqvae_forward_train(self.model, images, update_codebook=True)
         recons_loss = F.l1_loss(reconstruction.float(), images.float())
         total = recons_loss + quantization_loss

@@ -617,6 +617,23 @@ int ddpm_conv_wgrad_f32(const float *a, const float *dy, float *dw, int B, int C
 size_t ddpm_conv3d_wgrad_scratch_floats(int B, int Cin, int Cout, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int stride);
 int ddpm_conv3d_wgrad_f32(const float *a, const float *dy, float *dw, int B, int Cin, int Cout, int Di, int Hi, int Wi, int Do, int Ho,
                           int Wo, int stride, float *scratch, size_t scratch_floats, ddpm_stream_t stream);
+/* Weight gradient of the kernel-4, stride-2, padding-1 convolution in 2-D (dims = 2, Di ignored) or 3-D (dims = 3):
+ * dw[Cout, Cin, 4, 4(, 4)] (torch layout, overwritten) = sum over images and output positions o of dy[b, co, o] a[b, ci, 2 o + k - 1],
+ * a outside its extents read as 0.  a: [B, Cin, (Di,) Hi, Wi], dy: [B, Cout, (Di / 2,) Hi / 2, Wi / 2]; all extents even (need not
+ * be equal).  The TRANSPOSED convolution's weight gradient is the same sum with the operands swapped: a := its output gradient
+ * [B, Cout_t, 2 S], dy := its input [B, Cin_t, S] gives dw[Cin_t, Cout_t, 4 ...], torch's ConvTranspose layout.
+ * Cin % 64 == 0, Cout % 64 == 0 and Wi / 2 <= 64 run on the fp32 matrix pipe: 64 couts x 64 cins x 16 taps per workgroup, the
+ * (image, output position) stream split over `split` workgroups into `scratch` and reduced in a fixed order (no float atomics:
+ * bit-reproducible); 3-D as one launch of the 16-tap kernel per depth tap, an "image" = (batch item, output slice), depth taps
+ * outside the volume contributing nothing.  Every other shape (any channel counts: the 1-channel first / last VQ-VAE layers) takes the
+ * generic form: one workgroup per (cout, cin) pair and slice of the position stream, all taps in registers, fixed order;
+ * force_generic != 0 always selects it.  All global addressing is 64-bit: tensors beyond 2^31 elements are taken as they are.  A
+ * non-finite operand gives a non-finite result.  ddpm_conv_k4s2_wgrad_scratch_floats: what either form can use (0: none needed);
+ * ddpm_conv_k4s2_wgrad_split: workgroups per (cout, cin) tile of the matrix-pipe form (0: the shape has no such tiling).  */
+size_t ddpm_conv_k4s2_wgrad_scratch_floats(int B, int Cin, int Cout, int Di, int Hi, int Wi, int dims);
+int ddpm_conv_k4s2_wgrad_split(int B, int Cin, int Cout, int Di, int Hi, int Wi, int dims);
+int ddpm_conv_k4s2_wgrad_f32(const float *a, const float *dy, float *dw, int B, int Cin, int Cout, int Di, int Hi, int Wi, int dims,
+                             float *scratch, size_t scratch_floats, int force_generic, ddpm_stream_t stream);
 /* wt[Cin, Cout, taps] = w[Cout, Cin, taps] with the taps in reverse order (taps = k^2 or k^3: the kernel rotated by 180 degrees
  * about every axis) and the channel axes transposed: conv(dy, wt, padding = k / 2) is the input gradient of a stride-1
  * convolution (of a stride-2 one after ddpm_resample2_f32 / ddpm_resample3_f32(mode 2) of dy).  */
@@ -650,6 +667,8 @@ int ddpm_col_sum_f32(const float *in, float *out, int rows, int cols, int64_t ro
                      ddpm_stream_t stream);
 int ddpm_silu_f32(const float *x, float *y, int64_t n, ddpm_stream_t stream);
 int ddpm_silu_backward_f32(const float *x, const float *dy, float *dx, int64_t n, ddpm_stream_t stream);
+/* dx = dy where y > 0, else 0: the ReLU backward from the saved post-ReLU output (a tie at 0 carries no gradient; dx may alias dy)  */
+int ddpm_relu_backward_f32(const float *y, const float *dy, float *dx, int64_t n, ddpm_stream_t stream);
 /* out = alpha a + beta b (b may be NULL; out may alias a or b)  */
 int ddpm_axpby_f32(const float *a, const float *b, float *out, float alpha, float beta, int64_t n, ddpm_stream_t stream);
 /* x *= alpha in place (x 16-byte aligned); a non-finite value of x sets DDPM_STATUS_NONFINITE_GRAD in the device status word.  The

@@ -2,7 +2,10 @@
 device (one-hot, mm, EMA lines, mse_loss) -- same process, same box, medians of event-timed repetitions.  Results:
 profiles/vqvae_training.md.
 
-    python tools/vqvae_train_bench.py [--reps 50] [--full-step 1] [--terms 1]
+    python tools/vqvae_train_bench.py [--reps 50] [--full-step 1] [--terms 1] [--native 1]
+
+--native 1 times the full step on both routes of the encoder / decoder gradients in the same process -- the ATen route and
+DDPM_VQVAE_NATIVE=1 (vqvae_native.py) -- and the k4 s2 p1 weight-gradient kernel alone on the README's 256 -> 256 levels.
 
 --terms 1 also times the perceptual and the spectral term of DDPM_VQVAE_LOSS_TERMS (forward + backward w.r.t. the reconstruction)
 at the README configuration -- one 64^3 volume, 2.5-D LPIPS over three axes with half the slices kept -- on the HIP kernels and
@@ -139,6 +142,22 @@ def loss_terms_bench(dev, reps):
         print(f"  {name:<48s} {med:9.1f} [{lo:9.1f} .. {hi:9.1f}]")
 
 
+def k4s2_wgrad_bench(dev, reps):
+    """ddpm_conv_k4s2_wgrad_f32 on the README VQ-VAE's 256 -> 256 down-levels (batch 1 of 64^3: inputs of 32^3, 16^3, 8^3) and on the
+    1 -> 256 first layer (generic form): median time and the achieved rate over 2 B S_out Cout Cin 64 operations."""
+    from ddpm_ood_amd import train_ops as T
+
+    g = torch.Generator().manual_seed(1)
+    print(f"k4 s2 p1 weight gradient; median [min .. max] us over {reps} repetitions")
+    for cin, cout, n in ((256, 256, 32), (256, 256, 16), (256, 256, 8), (1, 256, 64)):
+        a = torch.randn(1, cin, n, n, n, generator=g).to(dev)
+        dy = torch.randn(1, cout, n // 2, n // 2, n // 2, generator=g).to(dev)
+        med, lo, hi = timed(lambda: T.conv_k4s2_wgrad(a, dy), reps)
+        flop = 2.0 * (n // 2) ** 3 * cout * cin * 64
+        print(f"  {cin:3d} -> {cout} at {n}^3 (split {T.conv_k4s2_wgrad_split(a, dy)}) {med:9.1f} [{lo:9.1f} .. {hi:9.1f}]  "
+              f"{flop / med / 1e6:7.2f} TFLOP/s")
+
+
 def full_step(dev, reps, terms=()):
     """One full training step at the README configuration (batch 1 of 64^3: the volume the test suite runs the README VQ-VAE on)
     with the quantiser step timed inside it; terms: the extra loss terms of DDPM_VQVAE_LOSS_TERMS, timed inside it too."""
@@ -195,7 +214,10 @@ def full_step(dev, reps, terms=()):
     for n in names:
         setattr(ops, n, orig[n])
     qm = statistics.median(per_step)
-    print(f"full training step ({' + '.join(('l1', 'quantisation') + tuple(terms))}), README VQ-VAE, batch 1 of 64^3 (64 latent positions): median {med / 1e3:.2f} ms "
+    from ddpm_ood_amd.vqvae_train import native_conv_gradients
+
+    print(f"full training step ({' + '.join(('l1', 'quantisation') + tuple(terms))}; conv gradients: "
+          f"{'native' if native_conv_gradients() else 'aten'}), README VQ-VAE, batch 1 of 64^3 (64 latent positions): median {med / 1e3:.2f} ms "
           f"[{lo / 1e3:.2f} .. {hi / 1e3:.2f}] over {reps} steps; quantiser (3 HIP entry points) {qm:.1f} us = {100 * qm / med:.2f} % of the step")
 
 
@@ -205,6 +227,8 @@ if __name__ == "__main__":
     ap.add_argument("--full-step", type=int, default=1)
     ap.add_argument("--quantiser", type=int, default=1, help="0: only the full step (e.g. under rocprofv3 --kernel-trace --stats)")
     ap.add_argument("--terms", type=int, default=0, help="1: time the perceptual and spectral loss terms, alone and inside the step")
+    ap.add_argument("--native", type=int, default=0, help="1: the full step on the ATen route and with DDPM_VQVAE_NATIVE=1, and the "
+                                                           "k4 s2 weight-gradient kernel alone")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.quantiser:
@@ -212,6 +236,18 @@ if __name__ == "__main__":
         quantiser(16384, 128, 2048, a.reps, dev)
     if a.full_step:
         full_step(dev, max(5, a.reps // 5))
+    if a.native:
+        import os
+
+        k4s2_wgrad_bench(dev, a.reps)
+        was = os.environ.get("DDPM_VQVAE_NATIVE")
+        for leg in ("0", "1", "0", "1"):  # alternating: the spread between equal legs is the noise
+            os.environ["DDPM_VQVAE_NATIVE"] = leg
+            full_step(dev, max(5, a.reps // 5))
+        if was is None:
+            del os.environ["DDPM_VQVAE_NATIVE"]
+        else:
+            os.environ["DDPM_VQVAE_NATIVE"] = was
     if a.terms:
         loss_terms_bench(dev, max(5, a.reps // 5))
         for terms in (("perceptual",), ("spectral",), ("perceptual", "spectral")):
