@@ -60,6 +60,30 @@ __device__ __forceinline__ void v_store_row_addtid(int m0base, const uint32_t (&
   }
 }
 
+// ---- Upsample (UP).  A 6-wide patch row or column of a nearest-x2 image starts at upsampled index 4 tc - 1, so it reads
+// [a, b, b, c, c, d] of the source (zero padding = a virtual source pixel).  With d1 = d2 and d3 = d4 the two halves of every
+// (p, q) pair of B^T are the same fp32 number: transform row / column 2 = p - q is an exact zero, 1 is p + p, 3 is fma(2, p, p),
+// 4 is fma(-2, p, p).  25 of the 36 positions are live; they are numbered pair 0 (rows 0, 5): s = 0 1 3 4 5 6 7 9 10 11, pair 1
+// (row 1): s = 0 1 3 4 5, pair 2 (rows 3, 4) as pair 0.  Live position idx (0..24) -> V byte offset in the chunk's V slot |
+// (6 row + column) << 16.  DESIGN.md 3.13.1.
+constexpr int w44r_up_job(int idx) {
+  const int t = idx < 10 ? 0 : idx < 15 ? 1 : 2;
+  const int k = idx - (t == 0 ? 0 : t == 1 ? 10 : 15);
+  const int s = k < 2 ? k : k < 7 ? k + 1 : k + 2;
+  const int row = t == 0 ? (s < 6 ? 0 : 5) : t == 1 ? 1 : (s < 6 ? 3 : 4);
+  return (t * kVSB + 2 * s * (kT * 16)) | ((row * 6 + s % 6) << 16);
+}
+// load_a_up() doubles the V byte offset into the U byte offset across all three row-pair slots, and the offset shares a word
+// with the position index
+static_assert(kUSB == 2 * kVSB && 3 * kVSB < 65536, "w44r_up_job: U offset = 2 x V offset, below bit 16");
+
+// one live position (pair T, position S of its 12) of a lane's channel pair into the V slot; M0 = slot + tile half (as below)
+template <int T, int S>
+__device__ __forceinline__ void v_store_pos_addtid(uint32_t hi, uint32_t lo) {
+  asm volatile("ds_write_addtid_b32 %0 offset:%1" ::"v"(hi), "n"(T * kVSB + (2 * S) * (kT * 16)) : "memory");
+  asm volatile("ds_write_addtid_b32 %0 offset:%1" ::"v"(lo), "n"(T * kVSB + (2 * S + 1) * (kT * 16)) : "memory");
+}
+
 // a wave-uniform pointer the compiler has moved to VGPRs (SGPR pressure) back into SGPRs for the scalar-load asm statements
 template <class T>
 __device__ __forceinline__ const T *uniform_ptr(const T *p) {
@@ -115,6 +139,19 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
   int ua = (3 * pg * 2 + lhi) * (kK * 16) + (cb * 32 + l31) * 16;
   // ---- V (LDS bytes): slot (chunk & 1) * kVCB + t * kVSB + (2 position + plane) * 512 + tile * 16
   int va = 3 * pg * (2 * kT * 16) + l31 * 16;
+  // ---- UP: the 25 live positions of a nearest-x2 image (w44r_up_job: transform row 2 and transform column 2 are exact zeros),
+  // 7 / 6 / 6 / 6 jobs over the four waves of a cout block.  upj[j] (wave-uniform) = job j's V byte offset inside a chunk's V
+  // slot (half its U byte offset inside the chunk's three U slots: kUSB = 2 kVSB) | its position index 6 row + column << 16.
+  int upj[7] = {0, 0, 0, 0, 0, 0, 0};
+  bool up7 = false;
+  if constexpr (UP) {
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+      upj[j] = __builtin_amdgcn_readfirstlane(pg == 0 ? w44r_up_job(j) : pg == 1 ? w44r_up_job(7 + j) : pg == 2 ? w44r_up_job(13 + j) : w44r_up_job(19 + (j < 6 ? j : 5)));
+    up7 = pg == 0;
+    ua = lhi * (kK * 16) + (cb * 32 + l31) * 16;
+    va = l31 * 16;
+  }
 
   auto barrier = [&]() __attribute__((always_inline)) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -122,6 +159,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
   };
   auto zero_accumulators = [&]() __attribute__((always_inline)) {
     zero_pinned_tiles();
+    if constexpr (UP) return;  // (no ninth tile)
     float z;  // (a literal zero vector is materialised THROUGH a0..a15 by hipcc: an opaque zero keeps it in arch VGPRs)
     asm volatile("v_mov_b32 %0, 0" : "=v"(z));
     acc8 = f32x16{z, z, z, z, z, z, z, z, z, z, z, z, z, z, z, z};
@@ -231,9 +269,102 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
     for (int q = 0; q < 6; ++q) split_pair(t0r[q], t1r[q], hi6[q], lo6[q]);
     v_store_row_addtid<6>(m0base, hi6, lo6);
   };
+  // UP: the 25 live positions from the four distinct values [a, b, c, d] per axis (patch rows / columns 0, 2, 4, 5 of the
+  // expanded tile; 1 = 2 and 3 = 4 hold the same numbers).  Six tasks of 8 / 8 / 9 positions x two tile halves:
+  //   K = 0: transform row 0 (5 positions) + row 1, columns 0 1 3      K = 1: row 5 (5) + row 4, columns 0 1 3
+  //   K = 2: row 3 (5) + row 4, columns 4 5 + row 1, columns 4 5
+  // Every expression is the one produce() / bt6() evaluate for that position, with the equal operand written once.  One
+  // exception: produce() forms transform row 0 as fma(0, q, wa) (bm = 0), this form takes wa itself.  Equal for every finite q;
+  // a non-finite q (a row-5 term) no longer turns the row-0 values into NaN (it still reaches the output through row 5), and
+  // wa = -0 keeps its sign.  DESIGN.md 3.13.1.
+  auto produce_up = [&](auto kc_, int cc) __attribute__((always_inline)) {
+    constexpr int K = decltype(kc_)::value;
+    asm volatile("" : "+v"(tb0));
+    const int pb0 = tb0 + (cc & 1) * 2 * g.HS;
+    float X[2][4], Y[2][4], Z[2][4];  // column-pass rows: X all five live columns, Y / Z the partial ones
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const float *p = P + pb0 + c * g.PCH;
+      float rb[4], rc[4], re[4];
+      auto row = [&](int r, float (&dst)[4]) __attribute__((always_inline)) {
+        const v4f lo = *reinterpret_cast<const v4f *>(p + r * g.PW);
+        const v2f_t hi = *reinterpret_cast<const v2f_t *>(p + r * g.PW + 4);
+        dst[0] = lo[0]; dst[1] = lo[2]; dst[2] = hi[0]; dst[3] = hi[1];
+      };
+      row(2, rb);
+      row(4, rc);
+      if (K == 0) row(0, re);
+      if (K == 1) row(5, re);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float w12 = __builtin_fmaf(-2.f, rb[q], __builtin_fmaf(-2.f, rb[q], rc[q]));    // rows (1, 2): p = q
+        const float w34 = __builtin_fmaf(-0.5f, rb[q], __builtin_fmaf(-0.5f, rb[q], rc[q]));  // rows (3, 4): p = q
+        if constexpr (K == 0) {
+          X[c][q] = __builtin_fmaf(4.f, re[q], __builtin_fmaf(-5.f, rb[q], rc[q]));
+          Y[c][q] = __builtin_fmaf(1.f, w12, w12);
+        } else if constexpr (K == 1) {
+          X[c][q] = __builtin_fmaf(4.f, rb[q], __builtin_fmaf(-5.f, rc[q], re[q]));
+          Y[c][q] = __builtin_fmaf(-2.f, w34, w34);
+        } else {
+          X[c][q] = __builtin_fmaf(2.f, w34, w34);
+          Y[c][q] = __builtin_fmaf(-2.f, w34, w34);
+          Z[c][q] = __builtin_fmaf(1.f, w12, w12);
+        }
+      }
+    }
+    // row pass: live columns 0 1 3 4 5 of bt6 on [a, b, b, c, c, d]
+    auto rp = [&](const float (&x)[4], float (&o)[5]) __attribute__((always_inline)) {
+      const float pp = __builtin_fmaf(-4.f, x[1], x[2]), rr = x[2] - x[1];
+      o[0] = __builtin_fmaf(4.f, x[0], __builtin_fmaf(-5.f, x[1], x[2]));
+      o[1] = pp + pp;
+      o[2] = __builtin_fmaf(2.f, rr, rr);
+      o[3] = __builtin_fmaf(-2.f, rr, rr);
+      o[4] = __builtin_fmaf(4.f, x[1], __builtin_fmaf(-5.f, x[2], x[3]));
+    };
+    auto st = [&](auto tc_, auto sc_, float v0, float v1) __attribute__((always_inline)) {
+      uint32_t h, l;
+      split_pair(v0, v1, h, l);
+      v_store_pos_addtid<decltype(tc_)::value, decltype(sc_)::value>(h, l);
+    };
+    using std::integral_constant;
+    const int m0base = __builtin_amdgcn_readfirstlane((cc & 1) * kVCB + (ptask & 1) * 256);
+    float a0[5], a1[5];
+    rp(X[0], a0);
+    rp(X[1], a1);
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 1" ::"s"(m0base));
+    constexpr int TX = K == 0 ? 0 : K == 1 ? 0 : 2, SX = K == 1 ? 6 : 0;
+    st(integral_constant<int, TX>{}, integral_constant<int, SX + 0>{}, a0[0], a1[0]);
+    st(integral_constant<int, TX>{}, integral_constant<int, SX + 1>{}, a0[1], a1[1]);
+    st(integral_constant<int, TX>{}, integral_constant<int, SX + 3>{}, a0[2], a1[2]);
+    st(integral_constant<int, TX>{}, integral_constant<int, SX + 4>{}, a0[3], a1[3]);
+    st(integral_constant<int, TX>{}, integral_constant<int, SX + 5>{}, a0[4], a1[4]);
+    rp(Y[0], a0);
+    rp(Y[1], a1);
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 1" ::"s"(m0base));
+    if constexpr (K == 2) {
+      st(I2{}, integral_constant<int, 10>{}, a0[3], a1[3]);
+      st(I2{}, integral_constant<int, 11>{}, a0[4], a1[4]);
+      rp(Z[0], a0);
+      rp(Z[1], a1);
+      asm volatile("s_mov_b32 m0, %0\n\ts_nop 1" ::"s"(m0base));
+      st(I1{}, integral_constant<int, 4>{}, a0[3], a1[3]);
+      st(I1{}, integral_constant<int, 5>{}, a0[4], a1[4]);
+    } else {
+      constexpr int TY = K == 0 ? 1 : 2, SY = K == 0 ? 0 : 6;
+      st(integral_constant<int, TY>{}, integral_constant<int, SY + 0>{}, a0[0], a1[0]);
+      st(integral_constant<int, TY>{}, integral_constant<int, SY + 1>{}, a0[1], a1[1]);
+      st(integral_constant<int, TY>{}, integral_constant<int, SY + 3>{}, a0[2], a1[2]);
+    }
+  };
   auto produce_task = [&](int cc) __attribute__((always_inline)) {
     if (ptask < 0) return;
     const int t = ptask >> 1;
+    if constexpr (UP) {
+      if (t == 0) produce_up(I0{}, cc);
+      else if (t == 1) produce_up(I1{}, cc);
+      else produce_up(I2{}, cc);
+      return;
+    }
     if (t == 0) produce(I0{}, cc);
     else if (t == 1) produce(I1{}, cc);
     else produce(I2{}, cc);
@@ -374,7 +505,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
   // (six jobs ahead; 9 jobs per chunk, ring of 6: the indices repeat every two chunks, hence the two-chunk loop body), Bh / Bl by
   // ds_read_b128 one job ahead.
   constexpr int kAR = 6;  // A-operand ring depth: a divisor of 18 (static indices over the two-chunk body)
-  h8 Ar[kAR];
+  h8 Ar[UP ? 7 : kAR];  // (UP: one register per job, a whole chunk ahead)
   auto load_a = [&](int cl, int jj) __attribute__((always_inline)) {  // job jj of chunk cl (clamped into the item: behind the last chunk a harmless repeat)
     const int t = jj / 3, i = jj - 3 * t;
     const int c2 = min(cl, NCHs - 1);
@@ -417,6 +548,58 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
     }
   };
 
+  // UP: the wave's 6 or 7 live jobs (upj); job j accumulates into pinned tile j, the ninth tile is not used.  A comes from
+  // Ar[j], requested one chunk ahead (right behind the job's MFMAs of the previous chunk); B one job ahead, as above.  The
+  // staging slices: job j < 6 activates rounds 2 j and 2 j + 1 of chunk cc + 2 (one per part) and requests the same rounds of
+  // chunk cc + 3 behind its second MFMA.
+  auto load_a_up = [&](int cl, int job) __attribute__((always_inline)) {
+    const int c2 = min(cl, NCHs - 1);
+    const v4i_t v = __builtin_bit_cast(v4i_t, __builtin_amdgcn_raw_buffer_load_b128(rs_u, ua, (ukt + 3 * c2) * kUSB + 2 * (job & 0xffff), 0));
+    return __builtin_bit_cast(h8, v);
+  };
+  auto mfma_chunk_up = [&](int cl, auto &&slice) __attribute__((always_inline)) {
+    asm volatile("" : "+v"(ua), "+v"(va));
+    const int vb = va + (cl & 1) * kVCB;
+    h8 Bh[2], Bl[2];
+    auto read_b = [&](int slot, int job) __attribute__((always_inline)) {
+      const int ad = vb + (job & 0xffff);
+      Bh[slot] = lds_b128(ad, 0);
+      Bl[slot] = lds_b128(ad, kT * 16);
+    };
+    auto job = [&](auto jc, auto lastc) __attribute__((always_inline)) {
+      constexpr int j = decltype(jc)::value;
+      constexpr bool last = decltype(lastc)::value;
+      if constexpr (!last) {
+        read_b((j + 1) & 1, upj[j + 1]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // outstanding LDS reads, oldest first: Bh(j), Bl(j) [, Bh(j + 1), Bl(j + 1)] (+ whatever the slices issued: newer)
+      mfma_pin_wait<last ? 1 : 3>(j, Ar[j], Bh[j & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      slice(j, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (last) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      else asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
+      mfma_pin(j, Ar[j], Bl[j & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      Ar[j] = load_a_up(cl + 1, upj[j]);
+      slice(j, 1);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    read_b(0, upj[0]);
+    job(I0{}, std::false_type{});
+    job(I1{}, std::false_type{});
+    job(I2{}, std::false_type{});
+    job(std::integral_constant<int, 3>{}, std::false_type{});
+    job(std::integral_constant<int, 4>{}, std::false_type{});
+    if (up7) {
+      job(std::integral_constant<int, 5>{}, std::false_type{});
+      job(std::integral_constant<int, 6>{}, std::true_type{});
+    } else {
+      job(std::integral_constant<int, 5>{}, std::true_type{});
+    }
+  };
+
   // static priority for the second-dispatched half of the workgroup: at equal priority the older wave of a SIMD wins every VALU
   // arbitration and waves 4-7 ran every segment ~15 % slower than their partners (MI355X_MICROARCH.md, "Two waves per SIMD", item 4)
   if (wave >= 4) asm volatile("s_setprio 1");
@@ -443,8 +626,14 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
       barrier();
     }
     W44R_FSTAMP(5)
+    if constexpr (UP) {
 #pragma unroll
-    for (int jj = 0; jj < kAR; ++jj) Ar[jj] = load_a(0, jj);
+      for (int jj = 0; jj < 6; ++jj) Ar[jj] = load_a_up(0, upj[jj]);
+      if (up7) Ar[6] = load_a_up(0, upj[6]);
+    } else {
+#pragma unroll
+      for (int jj = 0; jj < kAR; ++jj) Ar[jj] = load_a(0, jj);
+    }
     produce_task(0);
     zero_accumulators();
     W44R_FSTAMP(6)
@@ -470,6 +659,20 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
       const LoadCtx L = load_prep(cc + 3, n_cur, has_next);
       W44R_STAMP(1)
       asm volatile("" : "+v"(pix0), "+v"(pw0), "+v"(pixL), "+v"(pwL));
+      if constexpr (UP) {
+        mfma_chunk_up(cc, [&](int jj, int part) __attribute__((always_inline)) {
+          if (jj >= 6) return;
+          const int k = 2 * jj + part;
+#pragma unroll
+          for (int kk = 0; kk < NRT; ++kk)
+            if (kk == k) activate_round(SA{}, cc + 2, kk);
+          if (part == 1) {
+#pragma unroll
+            for (int kk = 0; kk < NRT; ++kk)
+              if (kk / 2 == jj) load_round(L, SL{}, kk);
+          }
+        });
+      } else
       mfma_chunk(parc, cc, [&](int jj, int part) __attribute__((always_inline)) {
         // part 0 runs between a job's two MFMAs, part 1 behind them.  Even jobs: two activation rounds of chunk cc + 2, one per
         // part (two independent fma -> exp -> rcp chains interleave; one round per job left each job waiting for a ~100-cycle
@@ -567,6 +770,20 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
       // the slabs are [xi][cout block][lane]: lane-linear, so the 36 stores are ds_write_addtid_b32 (address = M0 + offset +
       // 4 lane; twice the rate of ds_write_b32).  M0 = cout block + the wave's position row (x / 3) + slab pair; offsets: slab of
       // the pair, column x % 3.
+      // UP: tile j of this wave is live position upj[j] >> 16; the eleven dead positions have no tile and no slab entry
+      if constexpr (UP) {
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+#pragma unroll
+          for (int j = 0; j < 7; ++j) {
+            if (j == 6 && !up7) continue;
+            const int m0v = __builtin_amdgcn_readfirstlane(((upj[j] >> 16) * 128 + cb * 64 + hh * 2 * kXS) * 4);
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 1" ::"s"(m0v));
+            asm volatile("ds_write_addtid_b32 %0 offset:%1" ::"v"(read_pinned(16 * j + 4 * q + 2 * hh)), "n"(0) : "memory");
+            asm volatile("ds_write_addtid_b32 %0 offset:%1" ::"v"(read_pinned(16 * j + 4 * q + 2 * hh + 1)), "n"(kXS * 4) : "memory");
+          }
+        }
+      } else
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
 #pragma unroll
@@ -594,7 +811,12 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
         float w[2][6];
 #pragma unroll
         for (int jj = 0; jj < 6; ++jj) {  // columns of M through two rows of A^T
-          const float m1 = xr[(1 * 6 + jj) * 128], m2 = xr[(2 * 6 + jj) * 128], m3 = xr[(3 * 6 + jj) * 128],
+          if (UP && jj == 2) {  // (UP: M of transform column 2 and of transform row 2 is a literal zero)
+            w[0][jj] = 0.f;
+            w[1][jj] = 0.f;
+            continue;
+          }
+          const float m1 = xr[(1 * 6 + jj) * 128], m2 = UP ? 0.f : xr[(2 * 6 + jj) * 128], m3 = xr[(3 * 6 + jj) * 128],
                       m4 = xr[(4 * 6 + jj) * 128];
           if (h == 0) {
             const float m0 = xr[(0 * 6 + jj) * 128];
