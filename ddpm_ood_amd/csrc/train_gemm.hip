@@ -45,6 +45,8 @@ struct GemmP {
   float alpha, beta;
   int S, kchunk;  // S > 1: the K range is cut into S slices of kchunk (a multiple of kGK); slice sp of batch item z writes its raw
   float *part;    // sums to part[(z S + sp) M N + m N + n], gemm_splitk_reduce_kernel adds them in order and applies alpha / beta
+  int kofs, klim;  // S == 1: the launch multiplies k in [kofs, klim) -- [0, K), or one K slice of a product that wanted slabs and got no
+                   // scratch for them (ddpm_gemm_f32: the slices then run one after another, each adding into C)
 };
 
 constexpr int kGT = 64;   // C tile (rows and columns) per workgroup
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int z = blockIdx.z / p.S, sp = blockIdx.z - z * p.S;
   const int z0 = z / p.Z1, z1 = z - z0 * p.Z1;
-  const int kbeg = sp * p.kchunk, kend = p.S > 1 ? min(p.K, kbeg + p.kchunk) : p.K;
+  const int kbeg = p.kofs + sp * p.kchunk, kend = p.S > 1 ? min(p.K, kbeg + p.kchunk) : p.klim;
   const float *A = p.A + z0 * p.sAz0 + z1 * p.sAz1;
   const float *B = p.B + z0 * p.sBz0 + z1 * p.sBz1;
   float *C = p.C + z0 * p.sCz0 + z1 * p.sCz1;
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(256) void gemm_f32_v4_kernel(const GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int z = blockIdx.z / p.S, sp = blockIdx.z - z * p.S;
   const int z0 = z / p.Z1, z1 = z - z0 * p.Z1;
-  const int kbeg = sp * p.kchunk, kend = p.S > 1 ? min(p.K, kbeg + p.kchunk) : p.K;
+  const int kbeg = p.kofs + sp * p.kchunk, kend = p.S > 1 ? min(p.K, kbeg + p.kchunk) : p.klim;
   const float *A = p.A + z0 * p.sAz0 + z1 * p.sAz1;
   const float *B = p.B + z0 * p.sBz0 + z1 * p.sBz1;
   float *C = p.C + z0 * p.sCz0 + z1 * p.sCz1;
@@ -231,7 +233,7 @@ __global__ __launch_bounds__(256) void gemm_f16x3_kk_kernel(const GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int z = blockIdx.z / p.S, sp = blockIdx.z - z * p.S;
   const int z0 = z / p.Z1, z1 = z - z0 * p.Z1;
-  const int kbeg = sp * p.kchunk, kend = p.S > 1 ? min(p.K, kbeg + p.kchunk) : p.K;
+  const int kbeg = p.kofs + sp * p.kchunk, kend = p.S > 1 ? min(p.K, kbeg + p.kchunk) : p.klim;
   const float *A = p.A + z0 * p.sAz0 + z1 * p.sAz1;
   const float *B = p.B + z0 * p.sBz0 + z1 * p.sBz1;
   float *C = p.C + z0 * p.sCz0 + z1 * p.sCz1;
@@ -1063,10 +1065,16 @@ extern "C" int ddpm_gemm_f32(const ddpm_gemm_desc *g, ddpm_stream_t stream) {
   p.sCz0 = g->c_batch_outer; p.sCz1 = g->c_batch;
   p.alpha = g->alpha; p.beta = g->beta;
   p.S = 1; p.kchunk = g->K; p.part = nullptr;
+  p.kofs = 0; p.klim = g->K;
   int kchunk;
   const int S = gemm_ksplit(g, kchunk);
+  int serial = 1;  // launches that walk the K range one slice after another
   if (S > 1 && g->scratch && g->scratch_floats >= (size_t)S * g->batch * g->M * g->N) {
     p.S = S; p.kchunk = kchunk; p.part = g->scratch;
+  } else if (S > 1) {
+    // no room for the slabs: the same K slices, one launch each in slice order, every one after the first adding into C (beta = 1)
+    // -- an element's fp32 accumulation chains stay as short as the split launch's, so does the rounding; the scratch is not touched
+    serial = S; p.kchunk = kchunk;
   }
   hipStream_t s = as_stream(stream);
   const char *kname = "train_gemm_f32";
@@ -1092,15 +1100,22 @@ extern "C" int ddpm_gemm_f32(const ddpm_gemm_desc *g, ddpm_stream_t stream) {
                                                                                                             : 0;
   static const bool plain = getenv("DDPM_GEMM_V4") && atoi(getenv("DDPM_GEMM_V4")) == 0;  // (A/B switch)
   static const bool no_h = getenv("DDPM_GEMM_F16X3") && atoi(getenv("DDPM_GEMM_F16X3")) == 0;  // (A/B switch)
-  if (fa == 1 && fb == 1 && g->split_f16 && !plain && !no_h && split_f16_on(true)) {
-    hipLaunchKernelGGL(gemm_f16x3_kk_kernel, grid, dim3(256), 0, s, p);
-  } else if (fa && fb && !plain) {
-    if (fa == 1 && fb == 1) hipLaunchKernelGGL((gemm_f32_v4_kernel<true, true>), grid, dim3(256), 0, s, p);
-    else if (fa == 1) hipLaunchKernelGGL((gemm_f32_v4_kernel<true, false>), grid, dim3(256), 0, s, p);
-    else if (fb == 1) hipLaunchKernelGGL((gemm_f32_v4_kernel<false, true>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((gemm_f32_v4_kernel<false, false>), grid, dim3(256), 0, s, p);
-  } else {
-    hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, s, p);
+  for (int i = 0; i < serial; ++i) {
+    if (serial > 1) {
+      p.kofs = i * kchunk;
+      p.klim = std::min(g->K, p.kofs + kchunk);
+      if (i) p.beta = 1.f;
+    }
+    if (fa == 1 && fb == 1 && g->split_f16 && !plain && !no_h && split_f16_on(true)) {
+      hipLaunchKernelGGL(gemm_f16x3_kk_kernel, grid, dim3(256), 0, s, p);
+    } else if (fa && fb && !plain) {
+      if (fa == 1 && fb == 1) hipLaunchKernelGGL((gemm_f32_v4_kernel<true, true>), grid, dim3(256), 0, s, p);
+      else if (fa == 1) hipLaunchKernelGGL((gemm_f32_v4_kernel<true, false>), grid, dim3(256), 0, s, p);
+      else if (fb == 1) hipLaunchKernelGGL((gemm_f32_v4_kernel<false, true>), grid, dim3(256), 0, s, p);
+      else hipLaunchKernelGGL((gemm_f32_v4_kernel<false, false>), grid, dim3(256), 0, s, p);
+    } else {
+      hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, s, p);
+    }
   }
   if (p.S > 1) {
     const size_t n = (size_t)g->M * g->N * g->batch;

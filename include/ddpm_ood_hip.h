@@ -110,7 +110,8 @@ typedef struct ddpm_conv_desc {
   const float *w_wino;
   /* Optional scratch (ddpm_conv_scratch_floats): a launch with fewer work items than CUs (small batches; the F(4x4) kernel
    * at the 8x8 level) splits the channel stream of each item over 2 or 4 workgroups, whose partial outputs go to slabs of this buffer and are added in
-   * a fixed order by a second pass.  NULL / too small: the convolution runs unsplit (same result up to fp32 rounding). */
+   * a fixed order by a second pass.  NULL / too small: the launch takes the largest split whose slabs fit
+   * (none at all included: unsplit), or the next family of the table runs -- never more than scratch_floats; same result up to fp32 rounding. */
   float *scratch;
   size_t scratch_floats;
   /* Optional, 2-D 3x3 DDPM_CONV_NORMAL only: weights pre-transformed by ddpm_pack_wino44_weight_f32 (U = G g G^T, 6 x 6).
@@ -580,7 +581,9 @@ typedef struct ddpm_gemm_desc {
   float alpha, beta;
   /* Optional: ddpm_gemm_scratch_floats(g) floats.  A product whose (M, N, batch) grid leaves most of the chip idle while K is
    * long (a 1x1 convolution's weight gradient) is cut into K slices, one workgroup each, whose partial sums go here and are
-   * added in slice order by a second pass (deterministic).  NULL / too small: one workgroup walks the whole K range.  */
+   * added in slice order by a second pass (deterministic).  NULL / too small: the same K slices run as one launch each, in slice
+   * order, every one after the first adding into C -- an element's fp32 accumulation chains, and with them the rounding (2e-6
+   * of max |C| against float64 in the tests), stay those of the split launch; the scratch is not touched.  */
   float *scratch;
   size_t scratch_floats;
   /* != 0: the caller vouches that both operands sit in the f16 exponent range (|v| < 65 504; full precision for |v| >= 4e-3,
