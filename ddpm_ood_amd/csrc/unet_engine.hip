@@ -23,37 +23,138 @@
 
 namespace ddpm {
 
+// ---- packed weight forms ---------------------------------------------------------------------------------------------
+// Besides its torch-layout tensor a convolution keeps packed copies of its weight in the blob, one per kernel family that may
+// take it.  kForms (below) has a row per form: how large it is, how it is packed, which ddpm_conv_desc field carries it and
+// for which launches.  forms_wanted() says which forms a convolution asks for; allocation (ddpm_unet::alloc_conv),
+// ddpm_unet_set_param and Runner::conv are loops over the table and know no form by name.
+enum Form { F_PACKED, F_H1, F_D1S, F_FOLDED, F_WINO, F_WINO44, F_WINO44H, F_S2H, F_D3H, F_COUNT };  // in blob order
+enum Role { PLAIN, RESIDUAL, DOWNSAMPLER, UPSAMPLER };  // what a convolution is in the network (fused q / k / v, temb: PLAIN)
+constexpr size_t kAbsent = ~size_t(0);
+
+struct Forms {  // blob offsets (in floats) of a convolution's packed copies; kAbsent: it keeps no such copy
+  size_t off[F_COUNT];
+  Forms() { for (size_t &o : off) o = kAbsent; }
+  bool has(int f) const { return off[f] != kAbsent; }
+};
+
 struct ParamSlot {
   std::string name;
   int64_t numel = 0;
   size_t raw_off = 0;           // float offset of the torch-layout copy inside the blob
-  bool is_conv = false;         // also packed for the MFMA kernel when the shape allows it
-  size_t packed_base = 0;       // float offset of the (possibly shared) packed weight
-  bool has_folded = false;      // Upsample conv: also keep the folded (4 x 2x2-tap) form
-  size_t folded_base = 0;
-  bool has_wino = false;        // 3x3 stride-1 conv: also keep the Winograd-domain form
-  size_t wino_base = 0;
-  bool has_wino44 = false;      // ... and the F(4x4, 3x3) form
-  size_t wino44_base = 0;
-  bool has_wino44h = false;     // ... and its split-f16 form (conv_wino44h.hip); base in floats, 2 f16 per float
-  size_t wino44h_base = 0;
-  bool has_s2h = false;         // Downsample conv: split-f16 planes of the direct stride-2 kernel (conv_s2h.hip), in wino44h_base
-  bool has_d3h = false;         // stride-1 3x3 conv: split-f16 planes of the one-shot direct kernels (conv_d3s.hip)
-  bool has_d1s = false;         // 1x1 conv: split-f16 planes of the small-launch kernel (conv_d3s.hip), in d3h_base
-  size_t d3h_base = 0;
-  bool has_h1 = false;          // 1x1 conv: pre-split f16 planes of the DMA-fed kernel (conv1x1_dma.hip), in wino44h_base
+  Forms forms;                  // conv weights: the packed copies to refresh (those of the shared weight for a fused member)
   int Cout = 0, Cin = 0, ksize = 1, cout_offset = 0, Cout_total = 0;
   int dims = 2;                 // 3: [Cout, Cin, k, k, k] packed as k slabs of 2-D taps (one per depth tap)
   bool optional = false;
   bool set = false;
 };
 
-struct ConvRef {  // a conv-like op: weight (raw + packed) and bias locations in the blob
-  size_t w_raw = 0, w_packed = 0, bias = 0, w_folded = 0, w_wino = 0, w_wino44 = 0, w_wino44h = 0, w_d3h = 0;
-  bool has_packed = false, has_folded = false, has_wino = false, has_wino44 = false, has_wino44h = false, has_d3h = false;
+struct ConvRef {  // a conv-like op: weight (raw + packed forms) and bias locations in the blob
+  size_t w_raw = 0, bias = 0;
+  Forms forms;
   int Cin = 0, Cout = 0, ksize = 1;
   int dims = 2;
 };
+
+struct FormRow {
+  const char *name;
+  size_t (*floats)(int Cout, int Cin, int k, int dims);  // blob floats (two f16 per float), 0: the shape has no such form
+  int (*pack)(const float *src, float *dst, const ParamSlot &p, hipStream_t s);  // from the torch tensor `src` of parameter p
+  int member_align;  // a fused member may use the form if its Cout and cout_offset are multiples of this (0: whole weights only)
+  const float *ddpm_conv_desc::*f32;  // the descriptor field that carries it: one of these two
+  const uint16_t *ddpm_conv_desc::*f16;
+  unsigned modes2, modes3;  // the launches it is attached to, one bit per DDPM_CONV_* mode: 2-D (and 1x1) / 3-D kernels
+  bool (*enabled)();        // switch read when the engine is created (nullptr: none)
+};
+
+static bool small_launch_planes() { return sw().conv_d3s != 0; }  // DDPM_CONV_D3S=0: no planes for conv_d3s.hip
+static uint16_t *halves(float *p) { return reinterpret_cast<uint16_t *>(p); }
+constexpr unsigned kN = 1u << DDPM_CONV_NORMAL, kS = 1u << DDPM_CONV_STRIDE2, kU = 1u << DDPM_CONV_UPSAMPLE2;
+
+static const FormRow kForms[F_COUNT] = {
+    // MFMA layout (conv_mfma.hip); 3-D: one packed 2-D weight per depth tap, ONE launch walks the three slabs
+    {"packed",
+     [](int Cout, int Cin, int k, int dims) {
+       return packed_conv_weight_floats(Cout, Cin, k) ? (size_t)Cout * Cin * (dims == 3 ? k * k * k : k * k) : 0;
+     },
+     [](const float *src, float *dst, const ParamSlot &p, hipStream_t s) {
+       const int nkd = p.dims == 3 ? p.ksize : 1, taps = p.ksize * p.ksize;
+       const size_t slab = (size_t)p.Cout_total * p.Cin * taps;
+       int rc = 0;
+       for (int kd = 0; kd < nkd && !rc; ++kd)
+         rc = launch_pack_conv_weight(src, dst + kd * slab, p.Cout, p.Cin, p.ksize, p.cout_offset, p.Cout_total, s,
+                                      nkd > 1 ? nkd * taps : 0, taps * kd);
+       return rc;
+     },
+     1, &ddpm_conv_desc::w_packed, nullptr, ~0u, ~0u, nullptr},
+    // 1x1: pre-split f16 planes of the DMA-fed kernel (conv1x1_dma.hip, which also wants the packed form); travels in w_wino44h
+    {"h1",
+     [](int Cout, int Cin, int k, int) {
+       return k == 1 && packed_conv_weight_floats(Cout, Cin, 1) && conv1x1_h_weight_halves(Cout, Cin) ? (size_t)Cout * Cin : 0;
+     },
+     [](const float *src, float *dst, const ParamSlot &p, hipStream_t s) {
+       return launch_pack_conv1x1_h_weight(src, halves(dst), p.Cout, p.Cin, p.cout_offset, p.Cout_total, s);
+     },
+     1, nullptr, &ddpm_conv_desc::w_wino44h, kN, 0, nullptr},
+    // 1x1: split-f16 planes of the small-launch kernel (conv_d3s.hip) in whole 64-cout tiles; travels in w_d3h
+    {"d1s", [](int Cout, int Cin, int k, int) { return k == 1 ? (conv_d1s_weight_halves(Cout, Cin) + 1) / 2 : 0; },
+     [](const float *src, float *dst, const ParamSlot &p, hipStream_t s) {
+       return launch_pack_conv_d1s_weight(src, halves(dst), p.Cout, p.Cin, p.cout_offset, p.Cout_total, s);
+     },
+     64, nullptr, &ddpm_conv_desc::w_d3h, kN, 0, small_launch_planes},
+    // Upsample conv: nearest-x2 + 3x3 folded into 4 2x2-tap convolutions
+    {"folded", [](int Cout, int Cin, int k, int dims) { return k == 3 && dims == 2 ? folded_upsample_weight_floats(Cout, Cin) : 0; },
+     [](const float *src, float *dst, const ParamSlot &p, hipStream_t s) {
+       return launch_fold_upsample_weight(src, dst, p.Cout, p.Cin, s);
+     },
+     0, &ddpm_conv_desc::w_folded, nullptr, kU, 0, nullptr},
+    // stride-1 3x3: Winograd F(2x2) (on the upsampled image: 9 of 16 positions); 3-D: one F(2x2) slab per depth tap
+    {"wino", [](int Cout, int Cin, int k, int dims) { return k == 3 ? wino_weight_floats(Cout, Cin) * (dims == 3 ? 3 : 1) : 0; },
+     [](const float *src, float *dst, const ParamSlot &p, hipStream_t s) {
+       return launch_pack_wino_weight(src, dst, p.Cout, p.Cin, s, p.dims == 3 ? 3 : 1);
+     },
+     0, &ddpm_conv_desc::w_wino, nullptr, kN | kU, kN, nullptr},
+    // ... F(4x4) in fp32 (latent volumes, 8^3, have no F(4x4) tiling: 2-D only, as the two forms below)
+    {"wino44", [](int Cout, int Cin, int k, int dims) { return k == 3 && dims == 2 ? wino44_weight_floats(Cout, Cin) : 0; },
+     [](const float *src, float *dst, const ParamSlot &p, hipStream_t s) {
+       return launch_pack_wino44_weight(src, dst, p.Cout, p.Cin, s);
+     },
+     0, &ddpm_conv_desc::w_wino44, nullptr, kN, 0, nullptr},
+    // ... and F(4x4) as split-f16 planes (conv_wino44h.hip), also on the upsampled image
+    {"wino44h", [](int Cout, int Cin, int k, int dims) { return k == 3 && dims == 2 ? wino44h_weight_halves(Cout, Cin) / 2 : 0; },
+     [](const float *src, float *dst, const ParamSlot &p, hipStream_t s) {
+       return launch_pack_wino44h_weight(src, halves(dst), p.Cout, p.Cin, s);
+     },
+     0, nullptr, &ddpm_conv_desc::w_wino44h, kN | kU, 0, nullptr},
+    // Downsample conv: split-f16 planes of the direct stride-2 kernel (conv_s2h.hip); travels in w_wino44h
+    {"s2h", [](int Cout, int Cin, int k, int dims) { return k == 3 && dims == 2 ? conv_s2h_weight_halves(Cout, Cin) / 2 : 0; },
+     [](const float *src, float *dst, const ParamSlot &p, hipStream_t s) {
+       return launch_pack_conv_s2h_weight(src, halves(dst), p.Cout, p.Cin, s);
+     },
+     0, nullptr, &ddpm_conv_desc::w_wino44h, kS, 0, nullptr},
+    // 3x3: split-f16 planes of the one-shot small-launch kernels (conv_d3s.hip: 8x8 / 16x16 / 32x32 layers of a few images)
+    {"d3h", [](int Cout, int Cin, int k, int dims) { return k == 3 && dims == 2 ? (conv_d3h_weight_halves(Cout, Cin) + 1) / 2 : 0; },
+     [](const float *src, float *dst, const ParamSlot &p, hipStream_t s) {
+       return launch_pack_conv_d3h_weight(src, halves(dst), p.Cout, p.Cin, s);
+     },
+     0, nullptr, &ddpm_conv_desc::w_d3h, kN | kS | kU, 0, small_launch_planes},
+};
+
+// The forms a convolution asks for (bit per Form); alloc_conv drops those whose size is 0 for the shape or whose switch is off.
+// conv_in / conv_out are stride-1 3x3 but PLAIN: no Winograd or d3h forms, whatever the size functions answer.
+static unsigned forms_wanted(Role role, int Cout, int Cin, int k, int dims) {
+  const auto bit = [](Form f) { return 1u << f; };
+  const unsigned plain = bit(F_PACKED) | bit(F_H1) | bit(F_D1S);
+  if (dims == 3) return role == RESIDUAL ? plain | bit(F_WINO) : plain;
+  switch (role) {
+    case RESIDUAL: return plain | bit(F_WINO) | bit(F_WINO44) | bit(F_WINO44H) | bit(F_D3H);
+    case DOWNSAMPLER: return plain | bit(F_S2H) | bit(F_D3H);
+    case UPSAMPLER:  // the kernels that index the upsampled image are only considered for a foldable weight
+      if (!kForms[F_FOLDED].floats(Cout, Cin, k, dims)) return plain;
+      return plain | bit(F_FOLDED) | bit(F_WINO) | bit(F_WINO44H) | bit(F_D3H);
+    default: return plain;
+  }
+}
 
 struct GNRef {
   size_t gamma = 0, beta = 0;
@@ -153,70 +254,42 @@ struct ddpm_unet {
     params.push_back(p);
     return (int)params.size() - 1;
   }
-  // conv / linear with its own weight and bias
-  // `dims` = spatial rank of the kernel (1x1 convs and Linears are rank-free: pass 2)
-  ConvRef add_conv(const std::string &prefix, int Cout, int Cin, int k, bool optional = false, int dims = 2) {
+  // a weight, its bias and the packed forms its role asks for.  `dims` = spatial rank of the kernel (1x1 convs and Linears are
+  // rank-free: 2)
+  ConvRef alloc_conv(int Cout, int Cin, int k, Role role = PLAIN, int dims = 2) {
     ConvRef r;
     if (k == 1) dims = 2;
     r.Cin = Cin; r.Cout = Cout; r.ksize = k; r.dims = dims;
-    const size_t n = (size_t)Cout * Cin * (dims == 3 ? k * k * k : k * k);
-    r.w_raw = alloc(n);
-    r.has_packed = packed_conv_weight_floats(Cout, Cin, k) != 0;
-    if (r.has_packed) r.w_packed = alloc(n);
-    const bool h1 = k == 1 && r.has_packed && conv1x1_h_weight_halves(Cout, Cin) != 0;  // skip connections, proj_attn
-    if (h1) {
-      r.has_wino44h = true;
-      r.w_wino44h = alloc(n);  // 2 f16 per weight
-    }
-    const size_t n1 = (k == 1 && sw().conv_d3s) ? conv_d1s_weight_halves(Cout, Cin) : 0;  // small-launch planes (conv_d3s.hip)
-    if (n1) {
-      r.has_d3h = true;
-      r.w_d3h = alloc((n1 + 1) / 2);
-    }
+    const unsigned want = forms_wanted(role, Cout, Cin, k, dims);
+    const auto alloc_forms = [&](int first, int last) {
+      for (int f = first; f < last; ++f) {
+        const FormRow &row = kForms[f];
+        const size_t n = (want >> f & 1) && (!row.enabled || row.enabled()) ? row.floats(Cout, Cin, k, dims) : 0;
+        if (n) r.forms.off[f] = alloc(n);
+      }
+    };
+    r.w_raw = alloc((size_t)Cout * Cin * (dims == 3 ? k * k * k : k * k));
+    alloc_forms(F_PACKED, F_FOLDED);
     r.bias = alloc(Cout);
-    const int wi = add_raw(prefix + ".weight", (int64_t)n, r.w_raw, optional);
-    params[wi].has_d1s = n1 != 0;
-    params[wi].d3h_base = r.w_d3h;
-    params[wi].is_conv = r.has_packed;
-    params[wi].packed_base = r.w_packed;
-    params[wi].has_h1 = h1;
-    params[wi].wino44h_base = r.w_wino44h;
-    params[wi].Cout = Cout; params[wi].Cin = Cin; params[wi].ksize = k;
-    params[wi].cout_offset = 0; params[wi].Cout_total = Cout; params[wi].dims = dims;
-    add_raw(prefix + ".bias", Cout, r.bias, optional);
+    alloc_forms(F_FOLDED, F_COUNT);
     return r;
   }
-  // member of a fused conv: rows [cout_offset, cout_offset + Cout) of a shared weight / bias
-  void add_fused_member(const std::string &prefix, const ConvRef &shared, int Cout, int cout_offset) {
-    const size_t n = (size_t)Cout * shared.Cin * shared.ksize * shared.ksize;
-    const int wi = add_raw(prefix + ".weight", (int64_t)n,
-                           shared.w_raw + (size_t)cout_offset * shared.Cin * shared.ksize * shared.ksize);
-    params[wi].is_conv = shared.has_packed;
-    params[wi].packed_base = shared.w_packed;
-    params[wi].has_h1 = shared.ksize == 1 && shared.has_wino44h;
-    params[wi].wino44h_base = shared.w_wino44h;
-    params[wi].has_d1s = shared.ksize == 1 && shared.has_d3h && Cout % 64 == 0 && cout_offset % 64 == 0;
-    params[wi].d3h_base = shared.w_d3h;
-    params[wi].Cout = Cout; params[wi].Cin = shared.Cin; params[wi].ksize = shared.ksize;
-    params[wi].cout_offset = cout_offset; params[wi].Cout_total = shared.Cout;
-    add_raw(prefix + ".bias", Cout, shared.bias + cout_offset);
+  // parameters of rows [cout_offset, cout_offset + Cout) of a convolution: all of them, or a member of a fused one
+  void add_conv_params(const std::string &prefix, const ConvRef &c, int Cout, int cout_offset, bool optional = false) {
+    const size_t per = (size_t)c.Cin * (c.dims == 3 ? c.ksize * c.ksize * c.ksize : c.ksize * c.ksize);
+    ParamSlot &p = params[add_raw(prefix + ".weight", (int64_t)(Cout * per), c.w_raw + cout_offset * per, optional)];
+    p.Cout = Cout; p.Cin = c.Cin; p.ksize = c.ksize; p.dims = c.dims;
+    p.cout_offset = cout_offset; p.Cout_total = c.Cout;
+    for (int f = 0; f < F_COUNT; ++f) {
+      const int a = kForms[f].member_align;
+      if (Cout == c.Cout || (a && Cout % a == 0 && cout_offset % a == 0)) p.forms.off[f] = c.forms.off[f];
+    }
+    add_raw(prefix + ".bias", Cout, c.bias + cout_offset, optional);
   }
-  ConvRef alloc_shared(int Cout_total, int Cin, int k) {
-    ConvRef r;
-    r.Cin = Cin; r.Cout = Cout_total; r.ksize = k;
-    const size_t n = (size_t)Cout_total * Cin * k * k;
-    r.w_raw = alloc(n);
-    r.has_packed = packed_conv_weight_floats(Cout_total, Cin, k) != 0;
-    if (r.has_packed) r.w_packed = alloc(n);
-    if (k == 1 && r.has_packed && conv1x1_h_weight_halves(Cout_total, Cin) != 0) {  // fused q / k / v (and the temb projections)
-      r.has_wino44h = true;
-      r.w_wino44h = alloc(n);
-    }
-    if (const size_t n1 = (k == 1 && sw().conv_d3s) ? conv_d1s_weight_halves(Cout_total, Cin) : 0) {
-      r.has_d3h = true;
-      r.w_d3h = alloc((n1 + 1) / 2);
-    }
-    r.bias = alloc(Cout_total);
+  // conv / linear with its own weight and bias
+  ConvRef add_conv(const std::string &prefix, int Cout, int Cin, int k, Role role = PLAIN, int dims = 2, bool optional = false) {
+    const ConvRef r = alloc_conv(Cout, Cin, k, role, dims);
+    add_conv_params(prefix, r, Cout, 0, optional);
     return r;
   }
   GNRef add_gn(const std::string &prefix, int C) {
@@ -237,47 +310,12 @@ static ResRef build_res(ddpm_unet *u, const std::string &prefix, int Cin, int Co
   ResRef r;
   r.Cin = Cin; r.Cout = Cout;
   r.n1 = u->add_gn(prefix + ".norm1", Cin);
-  r.c1 = u->add_conv(prefix + ".conv1.conv", Cout, Cin, 3, false, u->cfg.spatial_dims);
+  r.c1 = u->add_conv(prefix + ".conv1.conv", Cout, Cin, 3, RESIDUAL, u->cfg.spatial_dims);
   r.temb_off = temb_cursor;
   temb_members.emplace_back(prefix + ".time_emb_proj", Cout);
   temb_cursor += Cout;
   r.n2 = u->add_gn(prefix + ".norm2", Cout);
-  r.c2 = u->add_conv(prefix + ".conv2.conv", Cout, Cout, 3, false, u->cfg.spatial_dims);
-  {  // both 3x3 convs of a ResnetBlock are stride 1: Winograd-domain weights too (3-D: one F(2x2) slab per depth tap)
-    const bool d3 = u->cfg.spatial_dims == 3;
-    ConvRef *cr[2] = {&r.c1, &r.c2};
-    const char *nm[2] = {".conv1.conv.weight", ".conv2.conv.weight"};
-    for (int i = 0; i < 2; ++i) {
-      const size_t nw = wino_weight_floats(cr[i]->Cout, cr[i]->Cin) * (d3 ? 3 : 1);
-      if (!nw) continue;
-      cr[i]->has_wino = true;
-      cr[i]->w_wino = u->alloc(nw);
-      ParamSlot &ps = u->params[u->index[prefix + nm[i]]];
-      ps.has_wino = true;
-      ps.wino_base = cr[i]->w_wino;
-      if (d3) continue;  // latent volumes (8^3) have no F(4x4) tiling
-      if (const size_t n44 = wino44_weight_floats(cr[i]->Cout, cr[i]->Cin)) {
-        cr[i]->has_wino44 = true;
-        cr[i]->w_wino44 = u->alloc(n44);
-        ps.has_wino44 = true;
-        ps.wino44_base = cr[i]->w_wino44;
-      }
-      if (const size_t nh = wino44h_weight_halves(cr[i]->Cout, cr[i]->Cin)) {
-        cr[i]->has_wino44h = true;
-        cr[i]->w_wino44h = u->alloc(nh / 2);
-        ps.has_wino44h = true;
-        ps.wino44h_base = cr[i]->w_wino44h;
-      }
-      // direct split-f16 planes: read by the small-launch kernel (conv_d3s.hip: 8x8 / 16x16 layers of a few images) and by the
-      // direct split-f16 planes for the one-shot small-launch kernels (conv_d3s.hip)
-      if (const size_t nd = sw().conv_d3s ? conv_d3h_weight_halves(cr[i]->Cout, cr[i]->Cin) : 0) {
-        cr[i]->has_d3h = true;
-        cr[i]->w_d3h = u->alloc((nd + 1) / 2);
-        ps.has_d3h = true;
-        ps.d3h_base = cr[i]->w_d3h;
-      }
-    }
-  }
+  r.c2 = u->add_conv(prefix + ".conv2.conv", Cout, Cout, 3, RESIDUAL, u->cfg.spatial_dims);
   r.has_skip = Cin != Cout;
   if (r.has_skip) r.skip = u->add_conv(prefix + ".skip_connection.conv", Cout, Cin, 1);
   return r;
@@ -288,11 +326,11 @@ static AttnRef build_attn(ddpm_unet *u, const std::string &prefix, int C, int he
   a.C = C;
   a.heads = head_channels > 0 ? C / head_channels : 1;
   a.norm = u->add_gn(prefix + ".norm", C);
-  a.qkv = u->alloc_shared(3 * C, C, 1);
-  u->add_fused_member(prefix + ".to_q", a.qkv, C, 0);
-  u->add_fused_member(prefix + ".to_k", a.qkv, C, C);
-  u->add_fused_member(prefix + ".to_v", a.qkv, C, 2 * C);
-  a.proj = u->add_conv(prefix + ".proj_attn", C, C, 1, /*optional=*/!u->cfg.use_proj_attn);
+  a.qkv = u->alloc_conv(3 * C, C, 1);
+  u->add_conv_params(prefix + ".to_q", a.qkv, C, 0);
+  u->add_conv_params(prefix + ".to_k", a.qkv, C, C);
+  u->add_conv_params(prefix + ".to_v", a.qkv, C, 2 * C);
+  a.proj = u->add_conv(prefix + ".proj_attn", C, C, 1, PLAIN, 2, /*optional=*/!u->cfg.use_proj_attn);
   return a;
 }
 
@@ -330,7 +368,7 @@ extern "C" ddpm_unet *ddpm_unet_create(const ddpm_unet_config *cfg) {
   u->freqs_off = u->alloc(u->ch0 / 2);
   u->add_raw("freqs", u->ch0 / 2, u->freqs_off);
   const int sd = cfg->spatial_dims;
-  u->conv_in = u->add_conv("conv_in.conv", u->ch0, cfg->in_channels, 3, false, sd);
+  u->conv_in = u->add_conv("conv_in.conv", u->ch0, cfg->in_channels, 3, PLAIN, sd);
   u->te0 = u->add_conv("time_embed.0", u->ted, u->ch0, 1);
   u->te2 = u->add_conv("time_embed.2", u->ted, u->ted, 1);
 
@@ -351,23 +389,7 @@ extern "C" ddpm_unet *ddpm_unet_create(const ddpm_unet_config *cfg) {
       if (d.with_attn)
         d.att.push_back(build_attn(u, bp + ".attentions." + std::to_string(j), out_c, cfg->num_head_channels[i]));
     }
-    if (d.has_down) {
-      d.down = u->add_conv(bp + ".downsampler.op.conv", out_c, out_c, 3, false, sd);
-      if (const size_t nh = sd == 2 ? conv_s2h_weight_halves(out_c, out_c) : 0) {  // split-f16 planes for conv_s2h.hip
-        d.down.has_wino44h = true;
-        d.down.w_wino44h = u->alloc(nh / 2);
-        ParamSlot &ps = u->params[u->index[bp + ".downsampler.op.conv.weight"]];
-        ps.has_s2h = true;
-        ps.wino44h_base = d.down.w_wino44h;
-      }
-      if (const size_t nd = (sd == 2 && sw().conv_d3s) ? conv_d3h_weight_halves(out_c, out_c) : 0) {  // small launches (conv_d3s.hip)
-        d.down.has_d3h = true;
-        d.down.w_d3h = u->alloc((nd + 1) / 2);
-        ParamSlot &ps = u->params[u->index[bp + ".downsampler.op.conv.weight"]];
-        ps.has_d3h = true;
-        ps.d3h_base = d.down.w_d3h;
-      }
-    }
+    if (d.has_down) d.down = u->add_conv(bp + ".downsampler.op.conv", out_c, out_c, 3, DOWNSAMPLER, sd);
     u->down.push_back(d);
   }
   const int cm = cfg->num_channels[L - 1];
@@ -394,45 +416,18 @@ extern "C" ddpm_unet *ddpm_unet_create(const ddpm_unet_config *cfg) {
       if (b.with_attn)
         b.att.push_back(build_attn(u, bp + ".attentions." + std::to_string(j), out_c, cfg->num_head_channels[ri]));
     }
-    if (b.has_up) {
-      b.up = u->add_conv(bp + ".upsampler.conv.conv", out_c, out_c, 3, false, sd);
-      if (sd == 2 && folded_upsample_weight_floats(out_c, out_c)) {  // nearest-x2 + 3x3 folded into 4 2x2 convs
-        b.up.has_folded = true;
-        b.up.w_folded = u->alloc(folded_upsample_weight_floats(out_c, out_c));
-        ParamSlot &ps = u->params[u->index[bp + ".upsampler.conv.conv.weight"]];
-        ps.has_folded = true;
-        ps.folded_base = b.up.w_folded;
-        if (const size_t nw = wino_weight_floats(out_c, out_c)) {  // Winograd on the upsampled image (9 of 16 positions)
-          b.up.has_wino = true;
-          b.up.w_wino = u->alloc(nw);
-          ps.has_wino = true;
-          ps.wino_base = b.up.w_wino;
-        }
-        if (const size_t nh = wino44h_weight_halves(out_c, out_c)) {  // split-f16 F(4x4) on the upsampled image (conv_wino44h.hip)
-          b.up.has_wino44h = true;
-          b.up.w_wino44h = u->alloc(nh / 2);
-          ps.has_wino44h = true;
-          ps.wino44h_base = b.up.w_wino44h;
-        }
-        if (const size_t nd = sw().conv_d3s ? conv_d3h_weight_halves(out_c, out_c) : 0) {  // small launches (conv_d3s.hip)
-          b.up.has_d3h = true;
-          b.up.w_d3h = u->alloc((nd + 1) / 2);
-          ps.has_d3h = true;
-          ps.d3h_base = b.up.w_d3h;
-        }
-      }
-    }
+    if (b.has_up) b.up = u->add_conv(bp + ".upsampler.conv.conv", out_c, out_c, 3, UPSAMPLER, sd);
     u->up.push_back(b);
   }
   u->out_norm = u->add_gn("out.0", u->ch0);
-  u->conv_out = u->add_conv("out.2.conv", cfg->out_channels, u->ch0, 3, false, sd);
+  u->conv_out = u->add_conv("out.2.conv", cfg->out_channels, u->ch0, 3, PLAIN, sd);
 
   // all time_emb_proj Linears share one [sum Cout, 4 ch0] GEMM (emb is loop-invariant in a forward)
   u->temb_total = temb_cursor;
-  u->temb_all = u->alloc_shared(temb_cursor, u->ted, 1);
+  u->temb_all = u->alloc_conv(temb_cursor, u->ted, 1);
   int off = 0;
   for (auto &m : temb_members) {
-    u->add_fused_member(m.first, u->temb_all, m.second, off);
+    u->add_conv_params(m.first, u->temb_all, m.second, off);
     off += m.second;
   }
   return u;
@@ -476,48 +471,9 @@ extern "C" int ddpm_unet_set_param(ddpm_unet *h, const char *name, const float *
   hipStream_t s = as_stream(stream);
   int rc = launch_copy_f32(src, h->blob + p.raw_off, numel, s);
   if (rc) return rc;
-  if (p.is_conv && p.dims == 3 && p.ksize == 3) {
-    const size_t slab = (size_t)p.Cout_total * p.Cin * 9;  // one packed 2-D weight per depth tap
-    for (int kd = 0; kd < 3 && !rc; ++kd)
-      rc = launch_pack_conv_weight(src, h->blob + p.packed_base + kd * slab, p.Cout, p.Cin, 3, p.cout_offset,
-                                   p.Cout_total, s, 27, 9 * kd);
-    if (rc) return rc;
-  } else if (p.is_conv) {
-    rc = launch_pack_conv_weight(src, h->blob + p.packed_base, p.Cout, p.Cin, p.ksize, p.cout_offset, p.Cout_total, s);
-    if (rc) return rc;
-  }
-  if (p.has_wino) {
-    rc = launch_pack_wino_weight(src, h->blob + p.wino_base, p.Cout, p.Cin, s, p.dims == 3 ? 3 : 1);
-    if (rc) return rc;
-  }
-  if (p.has_wino44) {
-    rc = launch_pack_wino44_weight(src, h->blob + p.wino44_base, p.Cout, p.Cin, s);
-    if (rc) return rc;
-  }
-  if (p.has_wino44h) {
-    rc = launch_pack_wino44h_weight(src, reinterpret_cast<uint16_t *>(h->blob + p.wino44h_base), p.Cout, p.Cin, s);
-    if (rc) return rc;
-  }
-  if (p.has_d3h) {
-    rc = launch_pack_conv_d3h_weight(src, reinterpret_cast<uint16_t *>(h->blob + p.d3h_base), p.Cout, p.Cin, s);
-    if (rc) return rc;
-  }
-  if (p.has_d1s) {
-    rc = launch_pack_conv_d1s_weight(src, reinterpret_cast<uint16_t *>(h->blob + p.d3h_base), p.Cout, p.Cin, p.cout_offset,
-                                     p.Cout_total, s);
-    if (rc) return rc;
-  }
-  if (p.has_s2h) {
-    rc = launch_pack_conv_s2h_weight(src, reinterpret_cast<uint16_t *>(h->blob + p.wino44h_base), p.Cout, p.Cin, s);
-    if (rc) return rc;
-  }
-  if (p.has_h1) {
-    rc = launch_pack_conv1x1_h_weight(src, reinterpret_cast<uint16_t *>(h->blob + p.wino44h_base), p.Cout, p.Cin, p.cout_offset,
-                                      p.Cout_total, s);
-    if (rc) return rc;
-  }
-  if (p.has_folded) {
-    rc = launch_fold_upsample_weight(src, h->blob + p.folded_base, p.Cout, p.Cin, s);
+  for (int f = 0; f < F_COUNT; ++f) {
+    if (!p.forms.has(f)) continue;
+    rc = kForms[f].pack(src, h->blob + p.forms.off[f], p, s);
     if (rc) return rc;
   }
   p.set = true;
@@ -590,7 +546,6 @@ struct Runner {
     ddpm_conv_desc d{};
     d.in1 = in1.p; d.C1 = in1.C;
     d.in2 = in2 ? in2->p : nullptr; d.C2 = in2 ? in2->C : 0;
-    d.w_packed = c.has_packed ? P(c.w_packed) : nullptr;
     d.w_raw = P(c.w_raw);
     d.bias = P(c.bias);
     d.gscale = gsc; d.gshift = gsh;
@@ -600,14 +555,12 @@ struct Runner {
     d.B = B; d.Cout = c.Cout;
     d.Hi = in1.H; d.Wi = in1.W; d.Ho = Ho; d.Wo = Wo;
     d.ksize = c.ksize; d.mode = mode; d.act = act;
-    if (mode == DDPM_CONV_UPSAMPLE2 && c.has_folded) d.w_folded = P(c.w_folded);
-    if ((mode == DDPM_CONV_NORMAL || mode == DDPM_CONV_UPSAMPLE2) && c.has_wino && c.dims == 2)
-      d.w_wino = P(c.w_wino);
-    if (mode == DDPM_CONV_NORMAL && c.has_wino44 && c.dims == 2) d.w_wino44 = P(c.w_wino44);
-    if ((mode == DDPM_CONV_NORMAL || mode == DDPM_CONV_STRIDE2 || mode == DDPM_CONV_UPSAMPLE2) && c.has_d3h && c.dims == 2) d.w_d3h = reinterpret_cast<const uint16_t *>(P(c.w_d3h));
-    if ((mode == DDPM_CONV_NORMAL || mode == DDPM_CONV_UPSAMPLE2 || mode == DDPM_CONV_STRIDE2) && c.has_wino44h && c.dims == 2)
-      d.w_wino44h = reinterpret_cast<const uint16_t *>(P(c.w_wino44h));
-    if (c.dims == 3 && c.ksize == 3 && mode == DDPM_CONV_NORMAL && c.has_wino) d.w_wino = P(c.w_wino);  // F(2x2) per depth tap
+    for (int f = 0; f < F_COUNT; ++f) {  // the packed forms this launch may use
+      const FormRow &row = kForms[f];
+      if (!c.forms.has(f) || !((c.dims == 3 ? row.modes3 : row.modes2) >> mode & 1)) continue;
+      if (row.f32) d.*row.f32 = P(c.forms.off[f]);
+      else d.*row.f16 = reinterpret_cast<const uint16_t *>(P(c.forms.off[f]));
+    }
     if (c.dims == 3 && c.ksize == 3) {
       // F.conv3d: ONE launch walks the (depth tap, channel group) chunks (w_packed = three depth slabs); a
       // volume of depth 1 (input depth <= 2^(levels-1)) only has its centre tap

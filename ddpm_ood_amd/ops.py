@@ -20,134 +20,82 @@ CONV_NORMAL, CONV_STRIDE2, CONV_UPSAMPLE2 = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
 
 
-def pack_conv_weight(weight: torch.Tensor) -> torch.Tensor | None:
-    """torch [Cout, Cin, k, k] (or [out, in]) -> MFMA-packed weight, or None if unpackable."""
+def _kernel_is(w, kshape) -> bool:
+    """Is w a [Cout, Cin, *kshape] weight?  (None in kshape: any extent; kshape None: any weight; (1, 1) also takes [out, in].)"""
+    if kshape is None or (kshape == (1, 1) and w.ndim != 4):
+        return True
+    return w.ndim == 2 + len(kshape) and all(k is None or k == e for k, e in zip(kshape, w.shape[2:]))
+
+
+def _pack(what, weight, kshape, size_fn, pack_fn, dtype=torch.float32, *, ksize_arg=False, member_args=False, zeros=False,
+          numel=None, size_first=False):
+    """The one pattern of the weight packers below: check the kernel shape -> ask lib.<size_fn>(Cout, Cin[, k]) (0: None) ->
+    allocate `numel(n)` (default n) elements -> lib.<pack_fn>(w, out, Cout, Cin[, k][, 0, Cout], stream).  member_args: the packer
+    takes (cout_offset, Cout_total) of a fused member; size_first: the size is asked before the shape is looked at."""
     lib = _lib.load()
     w = require_device_f32(weight, "weight")
-    cout, cin = w.shape[0], w.shape[1]
-    k = w.shape[2] if w.ndim == 4 else 1
-    n = lib.ddpm_packed_conv_weight_floats(cout, cin, k)
-    if n == 0:
+    if not size_first and not _kernel_is(w, kshape):
         return None
-    out = torch.empty(n, dtype=torch.float32, device=w.device)
-    check(lib.ddpm_pack_conv_weight_f32(ptr(w), ptr(out), cout, cin, k, 0, cout, stream_ptr()), "pack_conv_weight")
+    dims = (w.shape[0], w.shape[1]) + (((w.shape[2] if w.ndim == 4 else 1),) if ksize_arg else ())
+    n = getattr(lib, size_fn)(*dims)
+    if n == 0 or (size_first and not _kernel_is(w, kshape)):
+        return None
+    out = (torch.zeros if zeros else torch.empty)(numel(n) if numel else n, dtype=dtype, device=w.device)
+    member = (0, w.shape[0]) if member_args else ()
+    check(getattr(lib, pack_fn)(ptr(w), ptr(out), *dims, *member, stream_ptr()), what)
     return out
+
+
+def pack_conv_weight(weight: torch.Tensor) -> torch.Tensor | None:
+    """torch [Cout, Cin, k, k] (or [out, in]) -> MFMA-packed weight, or None if unpackable."""
+    return _pack("pack_conv_weight", weight, None, "ddpm_packed_conv_weight_floats", "ddpm_pack_conv_weight_f32", ksize_arg=True,
+                 member_args=True)
 
 
 def pack_wino44_weight(weight: torch.Tensor) -> torch.Tensor | None:
     """torch [Cout, Cin, 3, 3] -> F(4x4, 3x3) Winograd-domain weights (6 x 6 positions) in the MFMA layout."""
-    lib = _lib.load()
-    w = require_device_f32(weight, "weight")
-    if w.ndim != 4 or tuple(w.shape[2:]) != (3, 3):
-        return None
-    n = lib.ddpm_wino44_weight_floats(w.shape[0], w.shape[1])
-    if n == 0:
-        return None
-    out = torch.empty(n, dtype=torch.float32, device=w.device)
-    check(lib.ddpm_pack_wino44_weight_f32(ptr(w), ptr(out), w.shape[0], w.shape[1], stream_ptr()), "pack_wino44_weight")
-    return out
+    return _pack("pack_wino44_weight", weight, (3, 3), "ddpm_wino44_weight_floats", "ddpm_pack_wino44_weight_f32")
 
 
 def pack_wino_weight(weight: torch.Tensor) -> torch.Tensor | None:
     """torch [Cout, Cin, 3, 3] -> Winograd-domain weights U = G g G^T in the MFMA layout (None if unsupported)."""
-    lib = _lib.load()
-    w = require_device_f32(weight, "weight")
-    if w.ndim != 4 or tuple(w.shape[2:]) != (3, 3):
-        return None
-    n = lib.ddpm_wino_weight_floats(w.shape[0], w.shape[1])
-    if n == 0:
-        return None
-    out = torch.empty(n, dtype=torch.float32, device=w.device)
-    check(lib.ddpm_pack_wino_weight_f32(ptr(w), ptr(out), w.shape[0], w.shape[1], stream_ptr()), "pack_wino_weight")
-    return out
+    return _pack("pack_wino_weight", weight, (3, 3), "ddpm_wino_weight_floats", "ddpm_pack_wino_weight_f32")
 
 
 def fold_upsample_weight(weight: torch.Tensor) -> torch.Tensor | None:
     """torch [Cout, Cin, 3, 3] of an Upsample conv -> the 4 folded 2x2-tap weights (None if not foldable)."""
-    lib = _lib.load()
-    w = require_device_f32(weight, "weight")
-    n = lib.ddpm_folded_upsample_weight_floats(w.shape[0], w.shape[1])
-    if n == 0 or w.ndim != 4 or w.shape[2] != 3:
-        return None
-    out = torch.empty(n, dtype=torch.float32, device=w.device)
-    check(lib.ddpm_fold_upsample_weight_f32(ptr(w), ptr(out), w.shape[0], w.shape[1], stream_ptr()), "fold")
-    return out
+    return _pack("fold", weight, (3, None), "ddpm_folded_upsample_weight_floats", "ddpm_fold_upsample_weight_f32", size_first=True)
 
 
 def pack_wino44h_weight(weight: torch.Tensor) -> torch.Tensor | None:
     """torch [Cout, Cin, 3, 3] -> F(4x4, 3x3) Winograd-domain weights as split-f16 planes (hi = f16(2^10 U), lo = the
     remainder) in the order conv_wino44h.hip's LDS-DMA lands them; None without a tiling (Cout % 64, Cin % 16)."""
-    lib = _lib.load()
-    w = require_device_f32(weight, "weight")
-    if w.ndim != 4 or tuple(w.shape[2:]) != (3, 3):
-        return None
-    n = lib.ddpm_wino44h_weight_halves(w.shape[0], w.shape[1])
-    if n == 0:
-        return None
-    out = torch.empty(n, dtype=torch.float16, device=w.device)
-    check(lib.ddpm_pack_wino44h_weight(ptr(w), out.data_ptr(), w.shape[0], w.shape[1], stream_ptr()), "pack_wino44h_weight")
-    return out
+    return _pack("pack_wino44h_weight", weight, (3, 3), "ddpm_wino44h_weight_halves", "ddpm_pack_wino44h_weight", torch.float16)
 
 
 def pack_conv1x1_h_weight(w):
     """[Cout, Cin(, 1, 1)] -> the pre-split f16 planes of the DMA-fed 1x1 kernel (conv1x1_dma.hip), or None if Cout % 128 or
     Cin % 16.  Pass it as conv(..., wino44h=...) of a 1x1 convolution."""
-    lib = _lib.load()
-    w = require_device_f32(w, "weight")
-    if w.ndim == 4 and (w.shape[2] != 1 or w.shape[3] != 1):
-        return None
-    n = lib.ddpm_conv1x1_h_weight_halves(w.shape[0], w.shape[1])
-    if n == 0:
-        return None
-    out = torch.empty(n, dtype=torch.float16, device=w.device)
-    check(lib.ddpm_pack_conv1x1_h_weight(ptr(w), out.data_ptr(), w.shape[0], w.shape[1], stream_ptr()), "pack_conv1x1_h_weight")
-    return out
+    return _pack("pack_conv1x1_h_weight", w, (1, 1), "ddpm_conv1x1_h_weight_halves", "ddpm_pack_conv1x1_h_weight", torch.float16)
 
 
 def pack_conv_d3h_weight(w):
-    """[Cout, Cin, 3, 3] -> split-f16 planes of the direct 3x3 kernel (conv_d3h.hip), or None (Cout % 128, Cin % 8).  Pass it as
+    """[Cout, Cin, 3, 3] -> split-f16 planes of the direct 3x3 kernel (conv_d3s.hip), or None (Cout % 128, Cin % 8).  Pass it as
     conv(..., d3h=...)."""
-    lib = _lib.load()
-    w = require_device_f32(w, "weight")
-    if w.ndim != 4 or w.shape[2] != 3 or w.shape[3] != 3:
-        return None
-    n = lib.ddpm_conv_d3h_weight_halves(w.shape[0], w.shape[1])
-    if n == 0:
-        return None
-    out = torch.empty(n, dtype=torch.float16, device=w.device)
-    check(lib.ddpm_pack_conv_d3h_weight(ptr(w), out.data_ptr(), w.shape[0], w.shape[1], stream_ptr()), "pack_conv_d3h_weight")
-    return out
+    return _pack("pack_conv_d3h_weight", w, (3, 3), "ddpm_conv_d3h_weight_halves", "ddpm_pack_conv_d3h_weight", torch.float16)
 
 
 def pack_conv_d1s_weight(w):
     """[Cout, Cin, 1, 1] (or [Cout, Cin]) -> split-f16 planes of the small-launch 1x1 kernel (conv_d3s.hip), or None (Cout % 64,
     Cin % 128).  Pass it as conv(..., d3h=...) of a 1x1 convolution."""
-    lib = _lib.load()
-    w = require_device_f32(w, "weight")
-    if w.ndim == 4 and (w.shape[2] != 1 or w.shape[3] != 1):
-        return None
-    n = lib.ddpm_conv_d1s_weight_halves(w.shape[0], w.shape[1])
-    if n == 0:
-        return None
-    out = torch.zeros(n, dtype=torch.float16, device=w.device)
-    check(lib.ddpm_pack_conv_d1s_weight(ptr(w), out.data_ptr(), w.shape[0], w.shape[1], 0, w.shape[0], stream_ptr()),
-          "pack_conv_d1s_weight")
-    return out
+    return _pack("pack_conv_d1s_weight", w, (1, 1), "ddpm_conv_d1s_weight_halves", "ddpm_pack_conv_d1s_weight", torch.float16,
+                 member_args=True, zeros=True)
 
 
 def pack_conv_s2h_weight(w):
     """[Cout, Cin, 3, 3] -> split-f16 planes of the direct stride-2 kernel (conv_s2h.hip), or None if the shape has no tiling.
     Pass it as conv(..., mode=CONV_STRIDE2, wino44h=...)."""
-    lib = _lib.load()
-    w = require_device_f32(w, "weight")
-    if w.ndim != 4 or w.shape[2] != 3 or w.shape[3] != 3:
-        return None
-    n = lib.ddpm_conv_s2h_weight_halves(w.shape[0], w.shape[1])
-    if n == 0:
-        return None
-    out = torch.empty(n, dtype=torch.float16, device=w.device)
-    check(lib.ddpm_pack_conv_s2h_weight(ptr(w), out.data_ptr(), w.shape[0], w.shape[1], stream_ptr()), "pack_conv_s2h_weight")
-    return out
+    return _pack("pack_conv_s2h_weight", w, (3, 3), "ddpm_conv_s2h_weight_halves", "ddpm_pack_conv_s2h_weight", torch.float16)
 
 
 def conv(x, weight, bias=None, *, x2=None, gscale=None, gshift=None, act=ACT_NONE, mode=CONV_NORMAL,
@@ -267,25 +215,15 @@ def pack_conv3d_weight(weight: torch.Tensor) -> torch.Tensor:
 def pack_wino3d_weight(weight: torch.Tensor) -> torch.Tensor | None:
     """torch [Cout, Cin, 3, 3, 3] -> per-depth-tap Winograd-domain weights U_kd = G w[:, :, kd] G^T (None if the
     shape has no Winograd tiling: Cout % 64, Cin % 8)."""
-    lib = _lib.load()
-    w = require_device_f32(weight, "weight")
-    if w.ndim != 5 or tuple(w.shape[2:]) != (3, 3, 3) or lib.ddpm_wino_weight_floats(w.shape[0], w.shape[1]) == 0:
-        return None
-    out = torch.empty(3 * 16 * w.shape[0] * w.shape[1], dtype=torch.float32, device=w.device)
-    check(lib.ddpm_pack_wino3d_weight_f32(ptr(w), ptr(out), w.shape[0], w.shape[1], stream_ptr()), "pack_wino3d_weight")
-    return out
+    return _pack("pack_wino3d_weight", weight, (3, 3, 3), "ddpm_wino_weight_floats", "ddpm_pack_wino3d_weight_f32",
+                 numel=lambda n: 3 * n)
 
 
 def pack_wino44_3d_weight(weight: torch.Tensor) -> torch.Tensor | None:
     """torch [Cout, Cin, 3, 3, 3] -> per-depth-tap F(4x4, 3x3) weights U_kd = G w[:, :, kd] G^T, 6 x 6 (None if the shape
     has no tiling: Cout % 64, Cin % 8)."""
-    lib = _lib.load()
-    w = require_device_f32(weight, "weight")
-    if w.ndim != 5 or tuple(w.shape[2:]) != (3, 3, 3) or lib.ddpm_wino44_weight_floats(w.shape[0], w.shape[1]) == 0:
-        return None
-    out = torch.empty(3 * 36 * w.shape[0] * w.shape[1], dtype=torch.float32, device=w.device)
-    check(lib.ddpm_pack_wino44_weight3d_f32(ptr(w), ptr(out), w.shape[0], w.shape[1], stream_ptr()), "pack_wino44_3d_weight")
-    return out
+    return _pack("pack_wino44_3d_weight", weight, (3, 3, 3), "ddpm_wino44_weight_floats", "ddpm_pack_wino44_weight3d_f32",
+                 numel=lambda n: 3 * n)
 
 
 def pack_convT_weight(weight: torch.Tensor) -> torch.Tensor:
@@ -303,16 +241,8 @@ def pack_convT_weight(weight: torch.Tensor) -> torch.Tensor:
 
 def pack_wino44h_3d_weight(weight: torch.Tensor) -> torch.Tensor | None:
     """torch [Cout, Cin, 3, 3, 3] -> split-f16 F(4x4, 3x3) planes per depth tap (conv_wino44h.hip, 3-D form)."""
-    lib = _lib.load()
-    w = require_device_f32(weight, "weight")
-    if w.ndim != 5 or tuple(w.shape[2:]) != (3, 3, 3):
-        return None
-    n = lib.ddpm_wino44h_weight_halves(w.shape[0], w.shape[1])
-    if n == 0:
-        return None
-    out = torch.empty(3 * (n - 64) + 64, dtype=torch.float16, device=w.device)
-    check(lib.ddpm_pack_wino44h_weight3d(ptr(w), out.data_ptr(), w.shape[0], w.shape[1], stream_ptr()), "pack_wino44h_3d_weight")
-    return out
+    return _pack("pack_wino44h_3d_weight", weight, (3, 3, 3), "ddpm_wino44h_weight_halves", "ddpm_pack_wino44h_weight3d",
+                 torch.float16, numel=lambda n: 3 * (n - 64) + 64)  # the 64 trailing slots (scales) once, behind the three slabs
 
 
 def conv3d(x, weight, bias=None, *, act=ACT_NONE, out_act=ACT_NONE, residual=None, packed=None, stride: int = 1,
