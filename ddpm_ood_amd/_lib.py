@@ -128,6 +128,9 @@ SIGNATURES = {
     "ddpm_ancestral_step_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_int, C.c_int] + [C.c_float] * 5
                                 + [C.c_uint64, C.c_void_p, C.c_void_p]),
     "ddpm_randn_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "ddpm_vlb_noise_rows_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "ddpm_vlb_term_rows_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_int64, C.c_void_p]),
     "ddpm_clamp_mse_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "ddpm_vq_nearest_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
     "ddpm_vq_train_partials": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),

@@ -80,6 +80,36 @@ def score(val: pd.DataFrame, ind: pd.DataFrame, ood: pd.DataFrame, max_t: int = 
     return table, per_image, roc_auc_score(is_ood[known].astype(int), z[known])
 
 
+def score_likelihood(ind: pd.DataFrame, ood: pd.DataFrame, column: str = "nll"):
+    """AUROC of the likelihood baseline (likelihood_*.csv of likelihood.py): one row per image -- a repeated filename counts
+    once, the first copy, as in ``_rows`` -- in = 0, out = 1, and the score is the column itself: a higher NLL means more
+    out-of-distribution.  Returns (the table of both sets, AUROC)."""
+    table = pd.concat((ind[~ind.duplicated(subset=["filename"])].assign(type="in"),
+                       ood[~ood.duplicated(subset=["filename"])].assign(type="out")), ignore_index=True)
+    return table, roc_auc_score((table["type"] == "out").to_numpy().astype(int), table[column].to_numpy())
+
+
+def main_likelihood(args, out_data=None):
+    """``ood_detection.py --score likelihood``: the AUROC lines of ``main`` from likelihood_in.csv / likelihood_<name>.csv."""
+    model = args.model_name
+    run_dir = Path(args.output_dir) / model
+    print(f"Run directory: {str(run_dir)}")
+    out_dir = run_dir / "ood"
+    print("Score is the likelihood column nll")
+    if out_data is None:
+        out_data = out_datasets_for(model)
+    ind = pd.read_csv(out_dir / "likelihood_in.csv")
+    scores = []
+    for out_dataset in out_data:
+        df, auc = score_likelihood(ind, pd.read_csv(out_dir / f"likelihood_{out_dataset}.csv"))
+        print(f"n_in={(df['type'] == 'in').sum()} n_out={(df['type'] == 'out').sum()}")
+        scores.append(auc)
+    for o, s in zip(out_data, scores):
+        print(f"AUC for {model} vs {o}: {s * 100:.1f}")
+    print(f"Average AUC: {np.mean(scores) * 100:.1f}")
+    return dict(zip(out_data, scores))
+
+
 def main(args, out_data=None):
     model = args.model_name
     run_dir = Path(args.output_dir) / model

@@ -618,6 +618,121 @@ def ancestral_step(sample, model_output, *, sqrt_ac: float, sqrt_1m_ac: float, c
     return out, pred
 
 
+# ---- the variational bound over rows (likelihood.hip) ---------------------------------------
+
+VLB_COEF_STRIDE = 8
+
+
+def vlb_coef_table(table, device) -> torch.Tensor:
+    """The float64 [T, 6] table of ``DDPMScheduler.likelihood_coefficients`` as the fp32 [T, 8] device table the kernels
+    read (each entry rounded once, two pads)."""
+    tab = np.asarray(table, dtype=np.float64)
+    if tab.ndim != 2 or tab.shape[1] != 6 or tab.shape[0] < 1:
+        raise ValueError(f"vlb_coef_table: expected a [T, 6] table, got {tab.shape}")
+    host = np.zeros((tab.shape[0], VLB_COEF_STRIDE), dtype=np.float32)
+    host[:, :6] = tab.astype(np.float32)
+    return torch.from_numpy(host).to(device)
+
+
+class VlbRows:
+    """(image, timestep) rows on the device: int32 ``src`` / ``t`` of one length, range-checked on the host BEFORE the
+    upload (the kernels cannot check them).  ``rows[a:b]`` is a view: one upload serves every forward of a bound."""
+
+    def __init__(self, row_src, row_t, n_images: int, num_timesteps: int, device):
+        src = np.asarray(row_src, dtype=np.int64).reshape(-1)
+        t = np.asarray(row_t, dtype=np.int64).reshape(-1)
+        if src.shape != t.shape or src.size == 0:
+            raise ValueError(f"vlb rows: {src.size} image indices for {t.size} timesteps")
+        if src.min() < 0 or src.max() >= int(n_images):
+            raise ValueError(f"vlb rows: row_src outside [0, {int(n_images)})")
+        if t.min() < 0 or t.max() >= int(num_timesteps):
+            raise ValueError(f"vlb rows: row_t outside [0, {int(num_timesteps)})")
+        self.n_images, self.num_timesteps = int(n_images), int(num_timesteps)
+        self.src = torch.empty(src.shape, dtype=torch.int32, device=device)
+        self.t = torch.empty(t.shape, dtype=torch.int32, device=device)
+        self.src.copy_(torch.from_numpy(src.astype(np.int32)))
+        self.t.copy_(torch.from_numpy(t.astype(np.int32)))
+
+    def __len__(self) -> int:
+        return int(self.src.shape[0])
+
+    def __getitem__(self, s: slice) -> "VlbRows":
+        if not isinstance(s, slice) or s.step not in (None, 1):
+            raise TypeError("VlbRows supports contiguous slices only")
+        out = object.__new__(VlbRows)
+        out.n_images, out.num_timesteps = self.n_images, self.num_timesteps
+        out.src, out.t = self.src[s], self.t[s]
+        if out.src.shape[0] == 0:
+            raise ValueError("vlb rows: empty slice")
+        return out
+
+
+def _vlb_args(x0, row_src, row_t, coef):
+    x0 = require_device_f32(x0, "x0")
+    coef = require_device_f32(coef, "coef")
+    if coef.dim() != 2 or coef.shape[1] != VLB_COEF_STRIDE:
+        raise ValueError(f"coef must be the [T, {VLB_COEF_STRIDE}] device table of vlb_coef_table, got {tuple(coef.shape)}")
+    N, T = int(x0.shape[0]), int(coef.shape[0])
+    if isinstance(row_src, VlbRows):
+        rows = row_src
+        if row_t is not None:
+            raise ValueError("row_t must be None when row_src is a VlbRows")
+        if rows.n_images != N or rows.num_timesteps != T:
+            raise ValueError(f"vlb rows were checked against ({rows.n_images}, {rows.num_timesteps}), not ({N}, {T})")
+    else:
+        rows = VlbRows(row_src, row_t, N, T, x0.device)
+    return x0, coef, rows, N, T
+
+
+def vlb_noise_rows(x0, noise, row_src, row_t, coef, out=None):
+    """x_t[r] = sqrt(abar_t) x0[src] + sqrt(1 - abar_t) noise[src] for the rows (src, t) = (row_src[r], row_t[r]): host
+    sequences, range-checked here (0 <= src < N, 0 <= t < T), or one ``VlbRows`` (then ``row_t`` is None).  ``coef``: the
+    device table of ``vlb_coef_table``.  Returns [R, ...] (written into ``out`` if given)."""
+    lib = _lib.load()
+    x0, coef, rows, N, T = _vlb_args(x0, row_src, row_t, coef)
+    noise = require_device_f32(noise, "noise")
+    if noise.shape != x0.shape:
+        raise ValueError(f"noise {tuple(noise.shape)} does not match x0 {tuple(x0.shape)}")
+    R = len(rows)
+    shape = (R,) + tuple(x0.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x0.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x0.device:
+        raise ValueError(f"out must be a contiguous fp32 {shape} tensor on {x0.device}")
+    check(lib.ddpm_vlb_noise_rows_f32(ptr(x0), ptr(noise), ptr(rows.src), ptr(rows.t), ptr(coef), T, ptr(out), R,
+                                      x0[0].numel(), stream_ptr()), "vlb_noise_rows")
+    return out
+
+
+def vlb_term_rows(x0, x_t, model_output, row_src, row_t, coef, *, prediction_type: str = "epsilon", clip_sample: bool = True,
+                  bin_width: float = 1.0 / 255.0, return_kl_map: bool = False, out=None):
+    """term[r] = the row mean of the bound's term at (row_src[r], row_t[r]) (ddpm_vlb_term_rows_f32): the KL of posterior and
+    predicted step for t > 0, the discretised-Gaussian decoder NLL for t = 0.  Rows as in ``vlb_noise_rows``.  ``out``: a
+    contiguous fp32 [R] device tensor to write into (a slice of a larger one will do).  Returns term, or (term, kl_map
+    [R, ...]) with ``return_kl_map``."""
+    lib = _lib.load()
+    x0, coef, rows, N, T = _vlb_args(x0, row_src, row_t, coef)
+    x_t = require_device_f32(x_t, "x_t")
+    model_output = require_device_f32(model_output, "model_output")
+    R = len(rows)
+    shape = (R,) + tuple(x0.shape[1:])
+    if tuple(x_t.shape) != shape or tuple(model_output.shape) != shape:
+        raise ValueError(f"x_t {tuple(x_t.shape)} / model_output {tuple(model_output.shape)} must be {shape}")
+    if prediction_type not in PREDICTION_TYPES:
+        raise ValueError(f"unknown prediction_type {prediction_type}")
+    if not float(bin_width) > 0.0:
+        raise ValueError("bin_width must be positive")
+    if out is None:
+        out = torch.empty((R,), dtype=torch.float32, device=x0.device)
+    elif tuple(out.shape) != (R,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x0.device:
+        raise ValueError(f"out must be a contiguous fp32 [{R}] tensor on {x0.device}")
+    kl_map = torch.empty(shape, dtype=torch.float32, device=x0.device) if return_kl_map else None
+    check(lib.ddpm_vlb_term_rows_f32(ptr(x0), ptr(x_t), ptr(model_output), ptr(rows.src), ptr(rows.t), ptr(coef), T,
+                                     PREDICTION_TYPES[prediction_type], int(bool(clip_sample)), float(bin_width), ptr(out),
+                                     ptr(kl_map), R, x0[0].numel(), stream_ptr()), "vlb_term_rows")
+    return (out, kl_map) if return_kl_map else out
+
+
 def clamp_mse_(orig, recon, b_scale: float = 1.0):
     """In place: recon <- clamp(recon / b_scale, 0, 1); returns per-image MSE [B]."""
     lib = _lib.load()

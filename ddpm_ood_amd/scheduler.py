@@ -88,6 +88,17 @@ def sampling_streams(row_ids, timestep: int):
     return [int(r) * STREAMS_PER_ROW + t for r in row_ids]
 
 
+LIKELIHOOD_STREAM = STREAMS_PER_ROW - 1
+
+
+def likelihood_streams(row_ids):
+    """Philox stream id of image b's noise in the variational bound: ``row_ids[b] * 65536 + 65535`` under ``sampling_key(seed)``
+    -- ONE noise per image, shared by every timestep.  ``sampling_streams`` uses t <= num_train_timesteps (x_T: t = T) and the
+    bound rejects num_train_timesteps >= 65535, so no sampling step, x_T draw or (by the key's bit 63) training step reads the
+    same (key, stream) pair."""
+    return [int(r) * STREAMS_PER_ROW + LIKELIHOOD_STREAM for r in row_ids]
+
+
 class DDPMScheduler(Scheduler):
     """``generative.networks.schedulers.DDPMScheduler``: constructor, ``add_noise``, ``set_timesteps`` and the ancestral
     ``step`` (Ho et al. 2020, eq. 7 and algorithm 2), the latter as ONE fused launch (ops.ancestral_step) with the noise drawn
@@ -114,6 +125,7 @@ class DDPMScheduler(Scheduler):
         self.num_inference_steps = None
         self._coef_cache = {}
         self._coef_tables = (None, None, None)
+        self._vlb_cache = None  # (tables, (variance type, device), fp32 [T, 8] device table of the bound's coefficients)
         self._stream_table = None  # (row ids, device, int64 [T + 1, B] device tensor of stream ids)
 
     def set_timesteps(self, num_inference_steps: int, device=None) -> None:
@@ -159,6 +171,50 @@ class DDPMScheduler(Scheduler):
         out = (a_t ** 0.5, (1.0 - a_t) ** 0.5, c0, ct, sigma)
         self._coef_cache[key] = out
         return out
+
+    def _tables64(self):
+        """(abar_t, abar_{t-1}, beta_t, alpha_t) as float64 arrays of the tables as they are now; abar_{t-1} = 1 at t = 0 (Q22)."""
+        a_t = self.alphas_cumprod.double().numpy()
+        a_p = np.concatenate([np.ones(1), a_t[:-1]])
+        return a_t, a_p, self.betas.double().numpy(), self.alphas.double().numpy()
+
+    def _get_variance(self, timestep: int) -> float:
+        """The variance of p(x_{t-1} | x_t) (float64): (1 - abar_{t-1}) / (1 - abar_t) beta_t floored at 1e-20 (fixed_small, so
+        1e-20 at t = 0) or beta_t (fixed_large)."""
+        t = int(timestep)
+        if not 0 <= t < self.num_train_timesteps:
+            raise ValueError(f"timestep {t} outside [0, {self.num_train_timesteps})")
+        return float(self.likelihood_coefficients(raw=True)[t, 4])
+
+    def _get_mean(self, timestep: int, x_0: torch.Tensor, x_t: torch.Tensor) -> torch.Tensor:
+        """c0 x_0 + ct x_t: the mean of q(x_{t-1} | x_t, x_0) for the true x_0, of p(x_{t-1} | x_t) for the predicted one.
+        Plain tensor arithmetic in the inputs' dtype (a helper for callers and tests; the bound itself runs in
+        ops.vlb_term_rows)."""
+        _, _, c0, ct, _ = self.step_coefficients(int(timestep))
+        return c0 * x_0 + ct * x_t
+
+    def likelihood_coefficients(self, raw: bool = False) -> np.ndarray:
+        """float64 [T, 6]: sqrt(abar_t), sqrt(1 - abar_t), c0, ct, 0.5 / var, var^-1/2 of every train timestep, from the tables
+        as they are AT CALL TIME (snr_shift_tables reassigns them), with c0, ct, abar_{t-1} as in ``step_coefficients`` and var
+        as in ``_get_variance``.  ``raw``: column 4 holds var itself and column 5 its logarithm."""
+        a_t, a_p, beta, alpha = self._tables64()
+        c0 = np.sqrt(a_p) * beta / (1.0 - a_t)
+        ct = np.sqrt(alpha) * (1.0 - a_p) / (1.0 - a_t)
+        var = np.maximum((1.0 - a_p) / (1.0 - a_t) * beta, 1e-20) if self.variance_type == "fixed_small" else beta.copy()
+        last = (var, np.log(var)) if raw else (0.5 / var, np.exp(-0.5 * np.log(var)))
+        return np.stack([np.sqrt(a_t), np.sqrt(1.0 - a_t), c0, ct, *last], axis=1)
+
+    def likelihood_coefficients_device(self, device) -> torch.Tensor:
+        """The fp32 [T, 8] device copy of ``likelihood_coefficients`` (ops.vlb_coef_table), cached per (tables, variance type,
+        device); the held tables keep their id() from being reused."""
+        tables = (self.alphas_cumprod, self.betas, self.alphas)
+        key = (self.variance_type, str(torch.device(device)))
+        hit = self._vlb_cache
+        if hit is not None and hit[1] == key and all(a is b for a, b in zip(tables, hit[0])):
+            return hit[2]
+        dev = ops.vlb_coef_table(self.likelihood_coefficients(), device)
+        self._vlb_cache = (tables, key, dev)
+        return dev
 
     def _streams(self, row_ids, timestep: int, device) -> torch.Tensor:
         """The [B] device array of stream ids of this step: a row of a [T + 1, B] table uploaded once per (row ids, device),

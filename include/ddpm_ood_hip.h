@@ -336,6 +336,24 @@ int ddpm_ancestral_step_f32(const float *sample, const float *model_output, floa
 int ddpm_randn_rows_f32(float *out, int B, int64_t row_numel, uint64_t seed, const uint64_t *row_streams,
                         ddpm_stream_t stream);
 
+/* DiffusionInferer.get_likelihood: the DDPM variational bound over ROWS (likelihood.hip, additive: the ABI stays 10).  A row is
+ * one (image, timestep) pair: row r reads image row_src[r] of x0 / noise ([N, row_numel]; the caller checks 0 <= row_src[r] < N,
+ * the kernels cannot) and entry row_t[r] (0 <= row_t[r] < T) of coef, a DEVICE table [T][8] of fp32:
+ *   { sqrt(abar_t), sqrt(1 - abar_t), c0, ct, 0.5 / var, var^-1/2, 0, 0 }.  row_src / row_t: DEVICE int32 [R].
+ *   x_t[r] = sqrt_ac * x0[src] + sqrt_1m_ac * noise[src]                    two products and one sum, each rounded          */
+int ddpm_vlb_noise_rows_f32(const float *x0, const float *noise, const int32_t *row_src, const int32_t *row_t,
+                            const float *coef, int T, float *x_t, int R, int64_t row_numel, ddpm_stream_t stream);
+/* term[r] = the mean over the row of
+ *   row_t[r] > 0:  (0.5 / var) (c0 (x0 - x0hat))^2                          KL of two Gaussians of one variance
+ *   row_t[r] = 0:  -log of the discretised Gaussian of mean c0 x0hat + ct x_t, scale var^1/2 and bins of bin_width
+ * with x0hat as in ddpm_ancestral_step_f32.  kl_map: NULL, or receives the per-element values [R, row_numel].  One workgroup per
+ * row and a fixed summation tree: term[r] depends on that row's data alone, bit for bit.  A non-finite model output sets
+ * DDPM_STATUS_NONFINITE_EPS.  Both calls: 16-byte accesses when row_numel % 4 == 0 and every base is 16-byte aligned, a scalar
+ * path otherwise; no workspace.                                                                                              */
+int ddpm_vlb_term_rows_f32(const float *x0, const float *x_t, const float *model_output, const int32_t *row_src,
+                           const int32_t *row_t, const float *coef, int T, int prediction_type, int clip_sample,
+                           float bin_width, float *term, float *kl_map, int R, int64_t row_numel, ddpm_stream_t stream);
+
 /* recon = clamp(recon * inv_b_scale... (recon / b_scale), 0, 1) in place and
  * mse[b] = mean((orig - recon)^2) (src/trainers/reconstruct.py:167-168,188-191).          */
 int ddpm_clamp_mse_f32(const float *orig, float *recon, float b_scale, float *mse, int B, int64_t chw,

@@ -17,6 +17,8 @@ def parse_args(argv=None):
                    help="extension: which Z-score feeds the AUROC (the reference hard-codes mse)")
     p.add_argument("--out_data", default=None,
                    help="extension: comma list of OOD set names (default: picked from --model_name)")
+    p.add_argument("--score", default="reconstruction", choices=["reconstruction", "likelihood"],
+                   help="extension: likelihood reads the likelihood_*.csv files of likelihood.py and ranks by NLL")
     return p.parse_args(argv)
 
 
@@ -27,4 +29,5 @@ if __name__ == "__main__":
 
     for model in args.model_name.split(","):
         args.model_name = model
-        ood.main(args, out_data=args.out_data.split(",") if args.out_data else None)
+        run = ood.main_likelihood if args.score == "likelihood" else ood.main
+        run(args, out_data=args.out_data.split(",") if args.out_data else None)
