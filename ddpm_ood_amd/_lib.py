@@ -144,7 +144,12 @@ SIGNATURES = {
     "ddpm_lpips_pack_conv_weight_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ddpm_lpips_conv_mfma_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
     "ddpm_lpips_layer_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
-    "ddpm_lpips_layer_backward_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
+    # ---- anomaly maps (additive: the ABI version stays)
+    "ddpm_sqerr_map_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_void_p]),
+    "ddpm_lpips_layer_map_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_int64, C.c_int64, C.c_void_p]),
+    "ddpm_lpips_map_upsample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_int] * 17
+                                    + [C.c_float, C.c_int, C.c_void_p]),
+    "ddpm_lpips_layer_backward_f32":(C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
     "ddpm_maxpool3s2_backward_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_int] * 4 + [C.c_void_p]),
     "ddpm_lpips_conv1_dgrad_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p]),
     "ddpm_spectral_partials": (C.c_size_t, [C.c_int64]),

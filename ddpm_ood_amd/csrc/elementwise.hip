@@ -6,6 +6,7 @@
 //   plms_step   :155-157   scheduler.step(model_output, step, reconstructions)
 //   clamp_mse   :167-168, :188-191   x / b_scale; clamp_(0, 1); square(orig - x).mean(non-batch)
 // Algorithmic bytes per element: add_noise 12, plms_step 8 + 4 * n_eps, clamp_mse 12.
+// Beside them, only with --anomaly_maps 1: sqerr_map, the per-pixel squared error clamp_mse reduces away.
 #include "common.h"
 
 namespace ddpm {
@@ -173,6 +174,69 @@ int launch_clamp_mse(const float *orig, float *recon, float b_scale, float *mse,
   return 0;
 }
 
+// ---- per-pixel squared error, averaged over channels (anomaly maps) ------------------------------
+// map[b, s] (+)= weight * (1 / C) * sum_c (a[b, c, s] - b[b, c, s])^2, channels in ascending order.  A thread owns V
+// adjacent pixels (V = 4: 16-byte accesses; V = 1: the scalar path), adjacent threads adjacent groups: every channel plane is
+// read as one coalesced stream.  Both forms do the same arithmetic per pixel, so their results carry the same bits.
+// Bytes per output pixel: 8 C + 4 (+ 4 when accumulating).
+template <int V>
+__global__ __launch_bounds__(256) void sqerr_map_kernel(const float *__restrict__ a, const float *__restrict__ b,
+                                                        float *__restrict__ map, int C, int64_t S, int64_t items,
+                                                        float weight, int accumulate) {
+  struct alignas(4 * V) Vec { float v[V]; };
+  const int64_t per_image = S / V;  // groups per image
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const float fc = (float)C;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += stride) {
+    const int64_t bi = i / per_image, s = (i - bi * per_image) * V;
+    const float *pa = a + bi * C * S + s, *pb = b + bi * C * S + s;
+    float acc[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[j] = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const Vec x = *reinterpret_cast<const Vec *>(pa + (int64_t)c * S);
+      const Vec y = *reinterpret_cast<const Vec *>(pb + (int64_t)c * S);
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float d = x.v[j] - y.v[j];
+        acc[j] += d * d;
+      }
+    }
+    Vec *o = reinterpret_cast<Vec *>(map + bi * S + s);
+    Vec r;
+    if (accumulate) r = *o;
+#pragma unroll
+    for (int j = 0; j < V; ++j) r.v[j] = (accumulate ? r.v[j] : 0.f) + weight * (acc[j] / fc);
+    *o = r;
+  }
+}
+
+static bool ranges_overlap(const void *p, double p_bytes, const void *q, double q_bytes) {
+  const double a0 = (double)(uintptr_t)p, b0 = (double)(uintptr_t)q;
+  return a0 < b0 + q_bytes && b0 < a0 + p_bytes;
+}
+
+int launch_sqerr_map(const float *a, const float *b, float *map, int B, int C, int64_t S, float weight, int accumulate,
+                     hipStream_t s) {
+  DDPM_CHECK_ARG(a && b && map, "sqerr_map: null pointer");
+  DDPM_CHECK_ARG(B > 0 && C > 0 && S > 0, "sqerr_map: B, C and S must be positive (got %d, %d, %lld)", B, C, (long long)S);
+  DDPM_CHECK_ARG((double)B * C * (double)S < 9.0e18, "sqerr_map: tensor too large");
+  const double in_bytes = 4.0 * B * C * (double)S, map_bytes = 4.0 * B * (double)S;
+  DDPM_CHECK_ARG(!ranges_overlap(map, map_bytes, a, in_bytes) && !ranges_overlap(map, map_bytes, b, in_bytes),
+                 "sqerr_map: map aliases an input");
+  const bool vec = (S & 3) == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)map) & 15) == 0;
+  const int64_t items = vec ? (int64_t)B * (S / 4) : (int64_t)B * S;
+  int64_t blocks = (items + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  ProfScope prof(s, "sqerr_map", 3.0 * B * C * (double)S, 4.0 * B * (double)S * (2 * C + 1 + (accumulate ? 1 : 0)));
+  if (vec)
+    hipLaunchKernelGGL(sqerr_map_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, a, b, map, C, S, items, weight, accumulate);
+  else
+    hipLaunchKernelGGL(sqerr_map_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, a, b, map, C, S, items, weight, accumulate);
+  DDPM_CHECK_LAUNCH();
+  return 0;
+}
+
 // ---- plain copy (parameter upload into the engine blob) -----------------------------------------
 __global__ void copy_kernel(const float *__restrict__ src, float *__restrict__ dst, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -220,4 +284,9 @@ extern "C" int ddpm_plms_step_f32(const float *sample, const float *e0, const fl
 extern "C" int ddpm_clamp_mse_f32(const float *orig, float *recon, float b_scale, float *mse, int B, int64_t chw,
                                   ddpm_stream_t stream) {
   return launch_clamp_mse(orig, recon, b_scale, mse, B, chw, as_stream(stream));
+}
+
+extern "C" int ddpm_sqerr_map_f32(const float *a, const float *b, float *map, int B, int C, int64_t S, float weight,
+                                  int accumulate, ddpm_stream_t stream) {
+  return launch_sqerr_map(a, b, map, B, C, S, weight, accumulate, as_stream(stream));
 }

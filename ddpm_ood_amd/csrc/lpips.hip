@@ -10,6 +10,7 @@
 //   maxpool3s2_kernel    MaxPool2d(3, 2)
 //   lpips_layer_kernel   unit-normalise both feature maps over channels, squared difference, 1x1 "lin" weights,
 //                        spatial mean, accumulated over the five layers into one score per image pair
+// and, only with --anomaly_maps 1 (spatial=True of the package), lpips_layer_map_*_kernel + lpips_map_upsample_kernel below.
 // This is 24 MFLOP per 32x32 image pair -- 6e-5 of a reconstruction -- so the kernels are written for clarity and
 // coalesced access, not tuned: weights of the block's 4 output channels are wave-uniform (scalar loads), a thread owns
 // one output position, adjacent threads adjacent positions.
@@ -98,6 +99,112 @@ __global__ __launch_bounds__(256) void lpips_layer_kernel(const float *__restric
   }
   const float tot = block_sum_256(acc, red) / (float)HW;
   if (tid == 0) out[n] = accumulate ? out[n] + tot : tot;
+}
+
+// ---- spatial LPIPS (anomaly maps): the per-position value lpips_layer_kernel averages away ----------------------------------
+// maps[n * row_stride + row_offset + p] = sum_c lin[c] (f0[n,c,p] / (|f0[n,:,p]| + 1e-10) - f1[n,c,p] / (|f1[n,:,p]| + 1e-10))^2.
+// Two forms, chosen by HW alone (never by N, so a row's bits do not depend on the batch it rides in):
+//   lpips_layer_map_pos_kernel    HW > kMapWaveMaxHW: a thread owns one position and walks the channels in ascending order --
+//                                 the arithmetic of lpips_layer_kernel's inner loops, coalesced across the threads of a row;
+//   lpips_layer_map_wave_kernel   small maps (AlexNet's 3x3 and 1x1 layers at 32^2 .. 64^2 inputs, where a thread per position
+//                                 would leave 63 lanes of 64 idle and read with a stride of C): a wave owns one position, lane l
+//                                 sums channels l, l + 64, ... in ascending order, the 64 partials meet in wave_sum's fixed
+//                                 butterfly.
+// Bytes per position: 16 C (both maps twice; the second pass hits L2) + 4.
+constexpr int kMapWaveMaxHW = 16;
+
+__global__ __launch_bounds__(256) void lpips_layer_map_pos_kernel(const float *__restrict__ f0, const float *__restrict__ f1,
+                                                                  const float *__restrict__ lin, float *__restrict__ maps,
+                                                                  int64_t npos, int C, int HW, int64_t row_stride,
+                                                                  int64_t row_offset) {
+  const int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x;  // (n, p)
+  if (i >= npos) return;
+  const int64_t n = i / HW;
+  const int p = (int)(i - n * HW);
+  const float *a = f0 + (size_t)n * C * HW, *b = f1 + (size_t)n * C * HW;
+  float s0 = 0.f, s1 = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float x = a[(size_t)c * HW + p], y = b[(size_t)c * HW + p];
+    s0 += x * x;
+    s1 += y * y;
+  }
+  const float r0 = 1.f / (sqrtf(s0) + 1e-10f), r1 = 1.f / (sqrtf(s1) + 1e-10f);
+  float d2 = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float d = a[(size_t)c * HW + p] * r0 - b[(size_t)c * HW + p] * r1;
+    d2 += lin[c] * (d * d);
+  }
+  maps[n * row_stride + row_offset + p] = d2;
+}
+
+__global__ __launch_bounds__(256) void lpips_layer_map_wave_kernel(const float *__restrict__ f0, const float *__restrict__ f1,
+                                                                   const float *__restrict__ lin, float *__restrict__ maps,
+                                                                   int64_t npos, int C, int HW, int64_t row_stride,
+                                                                   int64_t row_offset) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = blockIdx.x * (int64_t)4 + (threadIdx.x >> 6);  // (n, p): one per wave, wave-uniform
+  if (i >= npos) return;
+  const int64_t n = i / HW;
+  const int p = (int)(i - n * HW);
+  const float *a = f0 + (size_t)n * C * HW + p, *b = f1 + (size_t)n * C * HW + p;
+  float s0 = 0.f, s1 = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float x = a[(size_t)c * HW], y = b[(size_t)c * HW];
+    s0 += x * x;
+    s1 += y * y;
+  }
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  const float r0 = 1.f / (sqrtf(s0) + 1e-10f), r1 = 1.f / (sqrtf(s1) + 1e-10f);
+  float d2 = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float d = a[(size_t)c * HW] * r0 - b[(size_t)c * HW] * r1;
+    d2 += lin[c] * (d * d);
+  }
+  d2 = wave_sum(d2);
+  if (lane == 0) maps[n * row_stride + row_offset + p] = d2;
+}
+
+// out[n, y, x] (+)= weight * sum_k bilinear_k(y + oy, x + ox): every layer's h_k x w_k map of the packed row
+// [n, sum_k h_k w_k] resampled to Hfull x Wfull as nn.Upsample(size, mode="bilinear", align_corners=False) does
+// (source coordinate max(scale (dst + 0.5) - 0.5, 0) with scale = in / out in fp32; [RECALLED] lpips 0.1.4's spatial=True
+// path applies exactly this per layer before summing), layers in ascending k, in ONE launch.  A thread owns one output
+// pixel of the H x W window at (oy, ox); the low-resolution maps are a few hundred bytes per image and stay in cache, so
+// the traffic is the output: 4 (+ 4 when accumulating) bytes per pixel.
+struct LpipsMapLayers {
+  int n, h[5], w[5], off[5];
+};
+
+__device__ __forceinline__ void bilinear_axis(int dst, int in, float scale, int &i0, int &i1, float &l) {
+  const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
+  i0 = min((int)s, in - 1);
+  i1 = min(i0 + 1, in - 1);
+  l = i1 == i0 ? 0.f : s - (float)i0;  // both taps on one sample (a 1-wide map, the far edge): that sample, exactly
+}
+
+__global__ __launch_bounds__(256) void lpips_map_upsample_kernel(const float *__restrict__ maps, float *__restrict__ out,
+                                                                 const LpipsMapLayers L, int64_t total, int64_t row_stride,
+                                                                 int Hfull, int Wfull, int oy, int ox, int H, int W,
+                                                                 float weight, int accumulate) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < total; i += stride) {
+    const int64_t n = i / ((int64_t)H * W);
+    const int r = (int)(i - n * H * W), y = r / W, x = r - y * W;
+    const float *row = maps + n * row_stride;
+    float acc = 0.f;
+    for (int k = 0; k < L.n; ++k) {
+      const int h = L.h[k], w = L.w[k];
+      int y0, y1, x0, x1;
+      float ly, lx;
+      bilinear_axis(y + oy, h, (float)h / (float)Hfull, y0, y1, ly);
+      bilinear_axis(x + ox, w, (float)w / (float)Wfull, x0, x1, lx);
+      const float *m = row + L.off[k];
+      const float top = (1.f - lx) * m[y0 * w + x0] + lx * m[y0 * w + x1];
+      const float bot = (1.f - lx) * m[y1 * w + x0] + lx * m[y1 * w + x1];
+      acc += (1.f - ly) * top + ly * bot;
+    }
+    out[i] = accumulate ? out[i] + weight * acc : weight * acc;
+  }
 }
 
 // ---- the 5x5 layer on the fp32 MFMA pipe -------------------------------------------------------------------------------
@@ -273,9 +380,80 @@ int launch_lpips_layer(const float *f0, const float *f1, const float *lin, float
   return 0;
 }
 
+static bool lp_overlap(const void *p, double p_bytes, const void *q, double q_bytes) {
+  const double a0 = (double)(uintptr_t)p, b0 = (double)(uintptr_t)q;
+  return a0 < b0 + q_bytes && b0 < a0 + p_bytes;
+}
+
+int launch_lpips_layer_map(const float *f0, const float *f1, const float *lin, float *maps, int N, int C, int HW,
+                           int64_t row_stride, int64_t row_offset, hipStream_t s) {
+  DDPM_CHECK_ARG(f0 && f1 && lin && maps, "lpips_layer_map: null pointer");
+  DDPM_CHECK_ARG(N > 0 && C > 0 && HW > 0, "lpips_layer_map: N, C and HW must be positive (got %d, %d, %d)", N, C, HW);
+  DDPM_CHECK_ARG(row_offset >= 0 && row_offset + HW <= row_stride,
+                 "lpips_layer_map: %d positions at offset %lld do not fit a row of %lld", HW, (long long)row_offset,
+                 (long long)row_stride);
+  const double fbytes = 4.0 * N * C * (double)HW, mbytes = 4.0 * N * (double)row_stride;
+  DDPM_CHECK_ARG(!lp_overlap(maps, mbytes, f0, fbytes) && !lp_overlap(maps, mbytes, f1, fbytes) && !lp_overlap(maps, mbytes, lin, 4.0 * C),
+                 "lpips_layer_map: maps aliases an input");
+  const int64_t npos = (int64_t)N * HW;
+  const bool wave = HW <= kMapWaveMaxHW;
+  const int64_t blocks = wave ? (npos + 3) / 4 : (npos + 255) / 256;
+  DDPM_CHECK_ARG(blocks <= 0x7fffffff, "lpips_layer_map: too many positions");
+  ProfScope prof(s, "lpips_layer_map", 8.0 * npos * C, 16.0 * npos * C + 4.0 * npos);
+  if (wave)
+    hipLaunchKernelGGL(lpips_layer_map_wave_kernel, dim3((unsigned)blocks), dim3(256), 0, s, f0, f1, lin, maps, npos, C, HW,
+                       row_stride, row_offset);
+  else
+    hipLaunchKernelGGL(lpips_layer_map_pos_kernel, dim3((unsigned)blocks), dim3(256), 0, s, f0, f1, lin, maps, npos, C, HW,
+                       row_stride, row_offset);
+  DDPM_CHECK_LAUNCH();
+  return 0;
+}
+
+int launch_lpips_map_upsample(const float *maps, float *out, int N, int64_t row_stride, const LpipsMapLayers &L, int Hfull,
+                              int Wfull, int oy, int ox, int H, int W, float weight, int accumulate, hipStream_t s) {
+  DDPM_CHECK_ARG(maps && out, "lpips_map_upsample: null pointer");
+  DDPM_CHECK_ARG(N > 0 && row_stride > 0, "lpips_map_upsample: N and row_stride must be positive");
+  DDPM_CHECK_ARG(L.n >= 1 && L.n <= 5, "lpips_map_upsample: n_layers must be 1 .. 5 (got %d)", L.n);
+  for (int k = 0; k < L.n; ++k)
+    DDPM_CHECK_ARG(L.h[k] > 0 && L.w[k] > 0 && L.h[k] <= 4096 && L.w[k] <= 4096,
+                   "lpips_map_upsample: layer %d has the extent %d x %d", k, L.h[k], L.w[k]);
+  DDPM_CHECK_ARG((int64_t)L.off[L.n - 1] + L.h[L.n - 1] * L.w[L.n - 1] <= row_stride,
+                 "lpips_map_upsample: the layers do not fit a row of %lld", (long long)row_stride);
+  DDPM_CHECK_ARG(Hfull > 0 && Wfull > 0 && H > 0 && W > 0 && oy >= 0 && ox >= 0 && (int64_t)oy + H <= Hfull && (int64_t)ox + W <= Wfull,
+                 "lpips_map_upsample: the window %d x %d at (%d, %d) lies outside the full grid %d x %d", H, W, oy, ox, Hfull, Wfull);
+  const int64_t total = (int64_t)N * H * W;
+  DDPM_CHECK_ARG(!lp_overlap(out, 4.0 * total, maps, 4.0 * N * (double)row_stride), "lpips_map_upsample: out aliases maps");
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  ProfScope prof(s, "lpips_map_upsample", 12.0 * total * L.n, 4.0 * total * (accumulate ? 2 : 1) + 4.0 * N * (double)row_stride);
+  hipLaunchKernelGGL(lpips_map_upsample_kernel, dim3((unsigned)blocks), dim3(256), 0, s, maps, out, L, total, row_stride, Hfull,
+                     Wfull, oy, ox, H, W, weight, accumulate);
+  DDPM_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace ddpm
 
 using namespace ddpm;
+
+extern "C" int ddpm_lpips_layer_map_f32(const float *f0, const float *f1, const float *lin, float *maps, int N, int C, int HW,
+                                        int64_t row_stride, int64_t row_offset, ddpm_stream_t stream) {
+  return launch_lpips_layer_map(f0, f1, lin, maps, N, C, HW, row_stride, row_offset, as_stream(stream));
+}
+
+extern "C" int ddpm_lpips_map_upsample_f32(const float *maps, float *out, int N, int64_t row_stride, int n_layers, int h0, int w0,
+                                           int h1, int w1, int h2, int w2, int h3, int w3, int h4, int w4, int Hfull, int Wfull,
+                                           int oy, int ox, int H, int W, float weight, int accumulate, ddpm_stream_t stream) {
+  LpipsMapLayers L{n_layers, {h0, h1, h2, h3, h4}, {w0, w1, w2, w3, w4}, {0, 0, 0, 0, 0}};
+  // layer k of a row starts where layer k - 1 ends; extents beyond the launcher's limits (which it refuses) count as 0 here
+  for (int k = 1; k < 5 && k < n_layers; ++k) {
+    const bool ok = L.h[k - 1] > 0 && L.w[k - 1] > 0 && L.h[k - 1] <= 4096 && L.w[k - 1] <= 4096;
+    L.off[k] = L.off[k - 1] + (ok ? L.h[k - 1] * L.w[k - 1] : 0);
+  }
+  return launch_lpips_map_upsample(maps, out, N, row_stride, L, Hfull, Wfull, oy, ox, H, W, weight, accumulate,
+                                   as_stream(stream));
+}
 
 extern "C" int ddpm_lpips_conv_f32(const float *in, const float *w, const float *bias, const float *in_scale,
                                    const float *in_shift, float *out, int N, int Cx, int Cin, int H, int W, int Cout,

@@ -747,6 +747,31 @@ def clamp_mse_(orig, recon, b_scale: float = 1.0):
     return mse
 
 
+def _accumulator(out, shape, device, what):
+    """(out tensor, accumulate flag): a fresh buffer, or the caller's own contiguous fp32 `out` of `shape` to add into."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device), 0
+    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float32
+            or not out.is_contiguous() or out.device != device):
+        raise ValueError(f"{what}: out must be a contiguous float32 {tuple(shape)} tensor on {device}")
+    return out, 1
+
+
+def sqerr_map(a, b, weight: float = 1.0, out=None):
+    """out[n, *spatial] (+)= weight * mean over channels of (a - b)^2 for two [N, C, *spatial] tensors (2-D or 3-D): the
+    per-pixel values behind ``clamp_mse_``'s per-image number.  ``out`` given: accumulated into (it may not overlap a or b)."""
+    lib = _lib.load()
+    a = require_device_f32(a, "a")
+    b = require_device_f32(b, "b")
+    if a.shape != b.shape or a.ndim < 3:
+        raise ValueError(f"sqerr_map wants two equal [N, C, *spatial] tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, Cc = a.shape[:2]
+    out, acc = _accumulator(out, (B,) + tuple(a.shape[2:]), a.device, "sqerr_map")
+    check(lib.ddpm_sqerr_map_f32(ptr(a), ptr(b), ptr(out), B, Cc, int(np.prod(a.shape[2:], dtype=np.int64)), float(weight), acc,
+                                 stream_ptr()), "sqerr_map")
+    return out
+
+
 # ---- LPIPS-AlexNet pieces (src/losses/perceptual_loss.py:105-186) -------------------------------------
 
 def lpips_conv(x, weight, bias, stride: int, pad: int, relu: bool = True, in_scale=None, in_shift=None):
@@ -832,6 +857,57 @@ def lpips_layer(f0, f1, lin, out=None):
         out = torch.empty(N, dtype=torch.float32, device=f0.device)
     check(lib.ddpm_lpips_layer_f32(ptr(f0), ptr(f1), ptr(lin), ptr(out), N, Cc, H * W, int(acc), stream_ptr()),
           "lpips_layer")
+    return out
+
+
+def lpips_layer_map(f0, f1, lin, maps=None, row_offset: int = 0):
+    """The per-position value ``lpips_layer`` averages: maps[n, row_offset + p] = the lin-weighted squared difference of the
+    channel-normalised features at position p.  ``maps``: a contiguous fp32 [N, row_stride] device tensor (the packed row of
+    all five layers of a pair; written at ``row_offset``), or None for a fresh [N, H * W]."""
+    lib = _lib.load()
+    f0 = require_device_f32(f0, "f0")
+    f1 = require_device_f32(f1, "f1")
+    lin = require_device_f32(lin, "lin")
+    if f0.shape != f1.shape or f0.ndim != 4:
+        raise ValueError(f"feature maps differ in shape: {tuple(f0.shape)} vs {tuple(f1.shape)}")
+    N, Cc, H, W = f0.shape
+    if lin.numel() != Cc:
+        raise ValueError(f"lpips_layer_map: lin has {lin.numel()} weights for {Cc} channels")
+    if maps is None:
+        maps, row_offset = torch.empty((N, H * W), dtype=torch.float32, device=f0.device), 0
+    elif (not isinstance(maps, torch.Tensor) or maps.ndim != 2 or maps.shape[0] != N or maps.dtype != torch.float32
+          or not maps.is_contiguous() or maps.device != f0.device):
+        raise ValueError(f"lpips_layer_map: maps must be a contiguous float32 [{N}, row_stride] tensor on {f0.device}")
+    if row_offset < 0 or row_offset + H * W > maps.shape[1]:
+        raise ValueError(f"lpips_layer_map: {H * W} positions at offset {row_offset} do not fit a row of {maps.shape[1]}")
+    check(lib.ddpm_lpips_layer_map_f32(ptr(f0), ptr(f1), ptr(lin), ptr(maps), N, Cc, H * W, maps.shape[1], int(row_offset),
+                                       stream_ptr()), "lpips_layer_map")
+    return maps
+
+
+def lpips_map_upsample(maps, layer_sizes, full_size, window=None, weight: float = 1.0, out=None):
+    """out[n, y, x] (+)= weight * the sum over layers of the layer's map resampled to ``full_size`` = (Hfull, Wfull) the way
+    ``nn.Upsample(size, mode="bilinear", align_corners=False)`` does.  ``maps``: [N, row_stride], the layers of
+    ``layer_sizes`` = [(h_k, w_k), ...] (1 .. 5 of them) packed one after the other in each row; ``window`` = (oy, ox, H, W)
+    selects a part of the full grid (default: all of it).  ``out`` given: a contiguous fp32 [N, H, W] to add into."""
+    lib = _lib.load()
+    maps = require_device_f32(maps, "maps")
+    if maps.ndim != 2:
+        raise ValueError(f"lpips_map_upsample: maps must be [N, row_stride], got {tuple(maps.shape)}")
+    sizes = [(int(h), int(w)) for h, w in layer_sizes]
+    if not 1 <= len(sizes) <= 5:
+        raise ValueError(f"lpips_map_upsample: 1 .. 5 layers, got {len(sizes)}")
+    if sum(h * w for h, w in sizes) > maps.shape[1] or min(min(s) for s in sizes) < 1:
+        raise ValueError(f"lpips_map_upsample: layers {sizes} do not fit a row of {maps.shape[1]}")
+    Hf, Wf = (int(v) for v in full_size)
+    oy, ox, H, W = (0, 0, Hf, Wf) if window is None else (int(v) for v in window)
+    if min(oy, ox) < 0 or min(H, W) < 1 or oy + H > Hf or ox + W > Wf:
+        raise ValueError(f"lpips_map_upsample: window {(oy, ox, H, W)} lies outside the full grid {(Hf, Wf)}")
+    N = maps.shape[0]
+    out, acc = _accumulator(out, (N, H, W), maps.device, "lpips_map_upsample")
+    flat = [v for s in sizes + [(0, 0)] * (5 - len(sizes)) for v in s]
+    check(lib.ddpm_lpips_map_upsample_f32(ptr(maps), ptr(out), N, maps.shape[1], len(sizes), *flat, Hf, Wf, oy, ox, H, W,
+                                          float(weight), acc, stream_ptr()), "lpips_map_upsample")
     return out
 
 

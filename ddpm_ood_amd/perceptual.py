@@ -57,8 +57,9 @@ class _NetLinLayer(nn.Module):
 class LPIPS(nn.Module):
     CHNS = (64, 192, 384, 256, 256)
 
-    def __init__(self, seed: int = 1234, **_ignored):
+    def __init__(self, seed: int = 1234, spatial: bool = False, **_ignored):
         super().__init__()
+        self.spatial = bool(spatial)  # forward returns the [N, 1, H, W] map instead of its [N, 1, 1, 1] layer-wise means
         self.scaling_layer = _ScalingLayer()
         self.net = _Alex()
         self.lins = nn.ModuleList([_NetLinLayer(c) for c in self.CHNS])
@@ -156,24 +157,74 @@ class LPIPS(nn.Module):
             outs.append(h)
         return outs
 
-    def _forward_hip(self, in0, in1, normalize: bool):
+    @staticmethod
+    def pyramid_sizes(height: int, width: int):
+        """(h_k, w_k) of the five AlexNet feature maps of a height x width input: conv 11 / 4 / 2, then two MaxPool2d(3, 2)
+        (the 5x5 and 3x3 convolutions keep their extent).  32 -> 7, 3, 1, 1, 1; 64 -> 15, 7, 3, 3, 3; 24 -> 5, 2, 0."""
+        def conv1(e):
+            return (e + 4 - 11) // 4 + 1 if e + 4 >= 11 else 0
+
+        def pool(e):
+            return (e - 3) // 2 + 1 if e >= 3 else 0
+
+        s1 = (conv1(height), conv1(width))
+        s2 = (pool(s1[0]), pool(s1[1]))
+        s3 = (pool(s2[0]), pool(s2[1]))
+        return [s1, s2, s3, s3, s3]
+
+    def _forward_hip(self, in0, in1, normalize: bool, value: bool = True, spatial: bool = False, window=None, weight: float = 1.0,
+                     out=None):
+        """(value [N, 1, 1, 1] or None, map [N, 1, H, W] or None) from ONE feature pass.  The value comes from the same
+        lpips_layer calls whether or not the map is asked for.  Map: every layer's per-position distance into one packed
+        row per pair, then one launch that resamples the five layers to the input's extent (``window`` = (oy, ox, H, W) of
+        it) and sums them, times ``weight``, into ``out`` [N, H, W] if given."""
         from . import ops
 
         n = in0.shape[0]
+        full = tuple(in0.shape[2:])
+        if spatial:
+            sizes = self.pyramid_sizes(*full)
+            if min(min(s) for s in sizes) < 1:
+                raise ValueError(f"spatial LPIPS: a {full[0]} x {full[1]} input leaves an empty AlexNet layer "
+                                 f"({sizes}): nothing to resample")
         feats = self._features_hip(torch.cat([in0, in1], 0).contiguous(), normalize)
-        val = None
+        val = maps = None
+        if spatial:
+            assert [tuple(f.shape[2:]) for f in feats] == sizes
+            maps = torch.empty((n, sum(h * w for h, w in sizes)), dtype=torch.float32, device=in0.device)
+        offset = 0
         for k, f in enumerate(feats):
             lin = self.lins[k].model[1].weight.reshape(-1)
-            val = ops.lpips_layer(f[:n], f[n:], lin, val)
-        return val.reshape(n, 1, 1, 1)
+            if value:
+                val = ops.lpips_layer(f[:n], f[n:], lin, val)
+            if spatial:
+                ops.lpips_layer_map(f[:n], f[n:], lin, maps, offset)
+                offset += f.shape[2] * f.shape[3]
+        if spatial:
+            full_map = ops.lpips_map_upsample(maps, sizes, full, window, weight, out)
+            maps = full_map[:, None]
+        return (val.reshape(n, 1, 1, 1) if value else None), maps
 
-    def forward(self, in0, in1, normalize: bool = False):
+    @staticmethod
+    def _check(in0, in1):
         if not (isinstance(in0, torch.Tensor) and in0.is_cuda and in1.is_cuda):
             raise RuntimeError("LPIPS inputs must be ROCm device tensors: the HIP reconstruction path has no CPU fallback "
                                "(the CPU restatement is oracle/lpips.py, test infrastructure only)")
         if in0.shape != in1.shape or in0.shape[1] not in (1, 3):
             raise ValueError(f"LPIPS wants two equal [N, 1|3, H, W] batches, got {tuple(in0.shape)} and {tuple(in1.shape)}")
-        return self._forward_hip(in0.float(), in1.float(), normalize)
+
+    def forward(self, in0, in1, normalize: bool = False):
+        self._check(in0, in1)
+        val, amap = self._forward_hip(in0.float(), in1.float(), normalize, value=not self.spatial, spatial=self.spatial)
+        return amap if self.spatial else val
+
+    def forward_with_map(self, in0, in1, normalize: bool = False, window=None, weight: float = 1.0, out=None):
+        """(value [N, 1, 1, 1], map [N, 1, H, W]) from one feature pass: the value carries the bits of ``forward`` with
+        spatial=False.  ``window`` = (oy, ox, H, W) crops the map (an image that was padded for LPIPS); ``out`` [N, H, W]:
+        the map is added into it, times ``weight``, instead of returned fresh."""
+        self._check(in0, in1)
+        return self._forward_hip(in0.float(), in1.float(), normalize, value=True, spatial=True, window=window, weight=weight,
+                                 out=out)
 
 
 class PerceptualLoss(nn.Module):
@@ -194,7 +245,11 @@ class PerceptualLoss(nn.Module):
         ) if is_fake_3d else None
         self.keep_ratio = 1 - drop_ratio
         self.lpips_normalize = lpips_normalize
-        self.perceptual_function = LPIPS(**(lpips_kwargs or {}))
+        kwargs = {"spatial": spatial} if lpips_kwargs is None else dict(lpips_kwargs)  # (as the reference: its own kwargs win)
+        if dimensions == 3 and kwargs.get("spatial", False):
+            raise NotImplementedError("Spatial (per-pixel) perceptual maps are built for 2D inputs only: 2.5-D maps over the "
+                                      "views of a volume are not built.")
+        self.perceptual_function = LPIPS(**kwargs)
         self.perceptual_factor = 1
 
     @torch.no_grad()
@@ -211,6 +266,16 @@ class PerceptualLoss(nn.Module):
                 loss = self._calculate_fake_3d_loss(y, y_pred, permute_dims, view_dims) * self.perceptual_factor
             return loss
         return self.perceptual_function.forward(y, y_pred, normalize=self.lpips_normalize) * self.perceptual_factor
+
+    @torch.no_grad()
+    def forward_with_map(self, y: torch.Tensor, y_pred: torch.Tensor, window=None, weight: float = 1.0, out=None):
+        """2-D only: (the loss ``forward`` returns without ``spatial``, bit for bit; its per-pixel map [N, 1, H, W]) from one
+        feature pass -- ``LPIPS.forward_with_map`` has the arguments."""
+        if self.dimensions != 2:
+            raise NotImplementedError("Perceptual maps are built for 2D inputs only.")
+        val, amap = self.perceptual_function.forward_with_map(y.float(), y_pred.float(), normalize=self.lpips_normalize,
+                                                              window=window, weight=weight, out=out)
+        return val * self.perceptual_factor, amap
 
     def _calculate_fake_3d_loss(self, y, y_pred, permute_dims, view_dims):
         ys = y.permute(*permute_dims).contiguous().view(-1, *(y.shape[d] for d in view_dims))

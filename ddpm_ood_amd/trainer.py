@@ -130,6 +130,56 @@ def gather_scores(ids: torch.Tensor, scores: torch.Tensor, n_max: int = None):
     return out[:, 0].to(torch.int32), out[:, 1:].reshape(-1, n_t, 2), [int(c) for c in counts]
 
 
+def gather_rows(ids: torch.Tensor, rows: torch.Tensor, n_max: int = None):
+    """``gather_scores`` for rows of any trailing shape (the anomaly maps: fp32 [n_local, 2, H, W]): ONE all_gather of a dense
+    [n_max, 1 + row size] fp32 payload per rank, ids in column 0, short shards padded with id = -1 and the padding dropped
+    after the gather.  Returns (ids, rows, counts) concatenated rank-major on every rank."""
+    if not dist.is_initialized():
+        return ids, rows, [int(ids.shape[0])]
+    world = dist.get_world_size()
+    if n_max is None:
+        n_max = int(ids.shape[0]) if world == 1 else None
+    if n_max is None or ids.shape[0] > n_max:
+        raise ValueError(f"gather_rows: shard of {ids.shape[0]} rows does not fit the static capacity {n_max}")
+    if rows.shape[0] != ids.shape[0]:
+        raise ValueError(f"gather_rows: {rows.shape[0]} rows for {ids.shape[0]} ids")
+    if ids.numel() and int(ids.max()) >= 1 << 24:
+        raise ValueError(f"gather_rows: image id {int(ids.max())} is not exact in the fp32 payload (ids must be < 2^24)")
+    trailing = tuple(rows.shape[1:])
+    width = 1
+    for d in trailing:
+        width *= int(d)
+    payload = torch.full((n_max, width + 1), -1.0, dtype=torch.float32, device=rows.device)
+    payload[: ids.shape[0], 0] = ids.to(device=rows.device, dtype=torch.float32)
+    payload[: ids.shape[0], 1:] = rows.reshape(ids.shape[0], width)
+    dev = rows.device
+    if dist.get_backend() == "gloo" and payload.is_cuda:  # (the test hook of gather_scores)
+        payload = payload.cpu()
+    out = torch.empty((world * n_max, width + 1), dtype=torch.float32, device=payload.device)
+    dist.all_gather_into_tensor(out, payload)
+    out = out.to(dev)
+    valid = out[:, 0] >= 0
+    counts = valid.reshape(world, n_max).sum(dim=1).tolist()
+    out = out[valid]
+    return out[:, 0].to(torch.int32), out[:, 1:].reshape((-1,) + trailing), [int(c) for c in counts]
+
+
+def file_stem(filename) -> str:
+    """The ``filename`` column of the CSV (reconstruct.py:192-204 of the reference strips .nii / .gz as well)."""
+    return Path(filename).stem.replace(".nii", "").replace(".gz", "")
+
+
+def map_rows_in_csv_order(results, ids, name_of):
+    """Which gathered row belongs to which line of ``maps_<name>.npz``: (stems, picks) with ``stems`` the CSV's filenames in
+    their order of first appearance in ``results`` (the row dicts of ``rows_from_scores``) and ``picks[k]`` the position in
+    ``ids`` (the gathered image ids, rank-major) of the first row whose image carries the name ``stems[k]``."""
+    first = {}
+    for k, i in enumerate(ids):
+        first.setdefault(file_stem(name_of.get(int(i), str(int(i)))), k)
+    stems = list(dict.fromkeys(r["filename"] for r in results))
+    return stems, [first[s] for s in stems]
+
+
 def sub_batch(batch: dict, keep):
     """The loader batch restricted to the items `keep` (the numeric guard re-runs only the images that overflowed)."""
     img = batch["image"]
@@ -278,9 +328,16 @@ class BaseTrainer:
 
 class Reconstruct(BaseTrainer):
     def __init__(self, args):
+        # --anomaly_maps 1 (extension): per-pixel LPIPS and squared-error maps averaged over the t-starts, written next to the CSV
+        # (maps_<name>.npz).  bench.py and the tests build their Namespace by hand without the attribute: off.
+        self.anomaly_maps = bool(getattr(args, "anomaly_maps", 0))
+        if self.anomaly_maps and (int(args.spatial_dimension) != 2 or args.vqvae_checkpoint):
+            raise ValueError("--anomaly_maps 1: anomaly maps cover 2-D pixel-space models only (no --spatial_dimension 3, no "
+                             "--vqvae_checkpoint): 2.5-D and latent maps are not built")
         super().__init__(args)
         if not self.found_checkpoint:
             raise FileNotFoundError("Failed to find a saved model checkpoint.")
+        self.last_maps = None  # the maps of the last get_scores call (rank 0, --anomaly_maps 1), what _write puts into the .npz
         self.out_dir = self.run_dir / "ood"
         if self.rank == 0:
             self.out_dir.mkdir(exist_ok=True)
@@ -357,7 +414,8 @@ class Reconstruct(BaseTrainer):
             print(f"{dataset_name}")
         pl = self._perceptual()
         self.model.eval()
-        ids_all, names_all, scores_all = [], [], []
+        ids_all, names_all, scores_all, maps_all = [], [], [], []
+        self.last_maps = None
         t_values = [int(t) for t in reversed(self.make_scheduler().timesteps)[1::inference_skip_factor]
                     if (self.max_t_start is None or int(t) <= int(self.max_t_start))
                     and (self.t_start_subset is None or int(t) in set(self.t_start_subset))]
@@ -369,7 +427,7 @@ class Reconstruct(BaseTrainer):
             guard["vq_near_ties"] = 0  # latent positions whose two nearest codes were within 1e-5: candidates for a code flip
             _lib.vq_near_ties_read(clear=True)
         for batch in loader:
-            scores, t_values, n_r, n_f, B, dt = self._score_batch(batch, pl, inference_skip_factor)
+            scores, t_values, n_r, n_f, B, dt, maps = self._score_batch(batch, pl, inference_skip_factor)
             # numeric guard (include/ddpm_ood_hip.h): a non-finite eps / reconstruction / latent set the device status word.
             # With the split-f16 kernels on, that may be an operand beyond the f16 range rather than a genuine fp32
             # overflow: run the affected IMAGES again on the fp32-MFMA kernels; what is still non-finite then is written as
@@ -392,8 +450,10 @@ class Reconstruct(BaseTrainer):
                 prev = _lib.set_split_f16(False)
                 try:
                     sub = sub_batch(batch, bad)
-                    scores_b, t_values, _, n_f2, _, dt2 = self._score_batch(sub, pl, inference_skip_factor)
+                    scores_b, t_values, _, n_f2, _, dt2, maps_b = self._score_batch(sub, pl, inference_skip_factor)
                     scores[torch.as_tensor(bad, device=scores.device)] = scores_b
+                    if maps is not None:  # the maps follow the scores that are kept
+                        maps[torch.as_tensor(bad, device=maps.device)] = maps_b
                     n_f += n_f2
                     dt += dt2
                     word = _lib.status_read(clear=True)
@@ -411,6 +471,8 @@ class Reconstruct(BaseTrainer):
             n_recon += n_r
             n_fwd += n_f
             scores_all.append(scores)
+            if maps is not None:
+                maps_all.append(maps.cpu())  # one device->host copy per batch, after the batch's synchronisation
             ids_all.append(torch.tensor(batch["index"], dtype=torch.int32))
             names_all.extend(batch["image_meta_dict"]["filename_or_obj"])
             if quiet:
@@ -421,11 +483,13 @@ class Reconstruct(BaseTrainer):
                 print(f"Took {dt}s for a batch size of {B}")
         self.last_stats = {"reconstructions": n_recon, "unet_forwards": n_fwd,
                            "lpips_pretrained": bool(pl.perceptual_function.pretrained), **guard}
-        return self._collect(loader, dataset_name, t_values, ids_all, names_all, scores_all, quiet)
+        return self._collect(loader, dataset_name, t_values, ids_all, names_all, scores_all, quiet, maps_all)
 
     def _score_batch(self, batch, pl, inference_skip_factor):
         """One batch through reconstruct.py:97-204: every t-start's noise, PLMS trajectory, decode, MSE and LPIPS.
-        Returns (scores [B, n_t, 2] on the device, t values, reconstructions, UNet image-forwards, B, seconds)."""
+        Returns (scores [B, n_t, 2] on the device, t values, reconstructions, UNet image-forwards, B, seconds, maps): maps is
+        None, or with --anomaly_maps 1 the device tensor [B, 2, H, W] of the per-pixel LPIPS (channel 0) and squared error
+        (channel 1), each the mean over the t-starts."""
         n_recon = n_fwd = 0
         sched = self.make_scheduler()  # one per batch: PLMS history leaks across t-starts (Q3)
         timesteps = sched.timesteps
@@ -444,6 +508,11 @@ class Reconstruct(BaseTrainer):
         B = images.shape[0]
         idx = batch["index"]
         per_t = []
+        lp_map = se_map = None
+        if self.anomaly_maps:  # accumulated into once per t-start with weight 1 / n_t; no synchronisation inside the loop
+            lp_map = torch.zeros((B,) + tuple(images_original.shape[2:]), dtype=torch.float32, device=self.device)
+            se_map = torch.zeros_like(lp_map)
+            w_t = 1.0 / max(len(t_values), 1)
         for t_start in start_points:
             if self.reset_scheduler_per_t:
                 sched.set_timesteps(self.num_inference_steps)
@@ -474,7 +543,15 @@ class Reconstruct(BaseTrainer):
             if prof_decode:
                 _lib.load().ddpm_prof_enable(0)
             mse = ops.clamp_mse_(images_original, x, self.b_scale)  # x / b_scale, clamp_(0, 1), MSE
-            if self.spatial_dimension == 2:
+            if self.anomaly_maps:  # (2-D only) the same value from the same launches, and the map from the same features
+                ops.sqerr_map(images_original, x, w_t, out=se_map)
+                if images_original.shape[3] == 28:
+                    pd_, _ = pl.forward_with_map(F.pad(images_original, (2, 2, 2, 2)), F.pad(x, (2, 2, 2, 2)),
+                                                 window=(2, 2) + tuple(images_original.shape[2:]), weight=w_t, out=lp_map)
+                else:
+                    pd_, _ = pl.forward_with_map(images_original, x, weight=w_t, out=lp_map)
+                pd_ = pd_.reshape(B)
+            elif self.spatial_dimension == 2:
                 if images_original.shape[3] == 28:
                     pd_ = pl(F.pad(images_original, (2, 2, 2, 2)), F.pad(x, (2, 2, 2, 2)))
                 else:
@@ -486,14 +563,17 @@ class Reconstruct(BaseTrainer):
             per_t.append(torch.stack([pd_, mse], dim=1))
             n_recon += B
         scores = torch.stack(per_t, dim=1)  # [B, n_t, 2] on the device
+        maps = torch.stack([lp_map, se_map], dim=1) if self.anomaly_maps else None  # [B, 2, H, W]
         torch.cuda.current_stream().synchronize()
         t2 = time.time()
-        return scores, t_values, n_recon, n_fwd, B, t2 - t1
+        return scores, t_values, n_recon, n_fwd, B, t2 - t1, maps
 
-    def _collect(self, loader, dataset_name, t_values, ids_all, names_all, scores_all, quiet):
-        """reconstruct.py:238-250: everyone's rows on every rank, through ONE collective."""
+    def _collect(self, loader, dataset_name, t_values, ids_all, names_all, scores_all, quiet, maps_all=()):
+        """reconstruct.py:238-250: everyone's rows on every rank, through ONE collective (with --anomaly_maps 1 a second one
+        of the same scheme carries the maps; rank 0 keeps them in ``last_maps`` for ``_write``)."""
         if not scores_all and not self.ddp:
             return []
+        local_ids = torch.cat(ids_all) if ids_all else torch.zeros((0,), dtype=torch.int32)
         if scores_all:
             scores = torch.cat(scores_all, dim=0)
             ids = torch.cat(ids_all).to(self.device)
@@ -517,12 +597,40 @@ class Reconstruct(BaseTrainer):
             if int(os.environ["LOCAL_RANK"]) != 0 and not quiet:
                 sys.stdout = sys.stderr = open(os.devnull, "w")
         # the one device->host copy of the scores
-        return rows_from_scores(ids.cpu().tolist(), scores.cpu().numpy(), counts, t_values, name_of,
-                                loader.batch_size, dataset_name)
+        results = rows_from_scores(ids.cpu().tolist(), scores.cpu().numpy(), counts, t_values, name_of,
+                                   loader.batch_size, dataset_name)
+        if self.anomaly_maps:
+            self._collect_maps(loader, results, t_values, local_ids, ids.cpu().tolist(), name_of, maps_all)
+        return results
+
+    def _collect_maps(self, loader, results, t_values, local_ids, gathered_ids, name_of, maps_all):
+        """The maps of every rank's images in the CSV's order of first appearance (rank 0 keeps them: ``last_maps``)."""
+        if self.ddp and hasattr(loader, "all_names") and len(loader.all_names) < self.world:
+            # (every rank sees the same list and raises alike: a rank without an image does not know the maps' extent)
+            raise ValueError(f"--anomaly_maps 1: {len(loader.all_names)} images over {self.world} ranks leave a rank without "
+                             f"an image, and the maps' extent comes from the images")
+        if not maps_all:
+            raise ValueError("--anomaly_maps 1: this rank scored no batch (--drop_last on a short shard?): no maps to gather")
+        maps = torch.cat(list(maps_all), dim=0)
+        map_ids = gathered_ids
+        if self.ddp:
+            n_total = len(loader.all_names) if hasattr(loader, "all_names") else None
+            n_max = -(-n_total // self.world) if n_total is not None else None
+            gids, maps, _ = gather_rows(local_ids.to(self.device), maps.to(self.device), n_max)
+            map_ids, maps = gids.cpu().tolist(), maps.cpu()
+        if self.rank != 0:
+            return
+        stems, picks = map_rows_in_csv_order(results, map_ids, name_of)
+        maps = maps[torch.as_tensor(picks, dtype=torch.long)].numpy()
+        self.last_maps = {"filename": np.asarray(stems), "t": np.asarray(t_values, dtype=np.int64),
+                          "lpips_map": np.ascontiguousarray(maps[:, 0]), "mse_map": np.ascontiguousarray(maps[:, 1])}
 
     def _write(self, results_list, name):
         if self.rank == 0:
             pd.DataFrame(results_list).to_csv(self.out_dir / f"results_{name}.csv")
+            if self.anomaly_maps and self.last_maps is not None:  # filename [N], t [n_t], lpips_map / mse_map fp32 [N, H, W]
+                np.savez(self.out_dir / f"maps_{name}.npz", **self.last_maps)
+        self.last_maps = None
 
     def reconstruct(self, args):
         if bool(args.run_val):

@@ -359,6 +359,18 @@ int ddpm_vlb_term_rows_f32(const float *x0, const float *x_t, const float *model
 int ddpm_clamp_mse_f32(const float *orig, float *recon, float b_scale, float *mse, int B, int64_t chw,
                        ddpm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Anomaly maps (--anomaly_maps 1): the per-pixel values behind the two image-level scores.  Entry points
+ * added without an ABI bump; no workspace, no size function; every pointer but the stream is a device buffer.
+ * ---------------------------------------------------------------------------------- */
+/* map[b, s] = (accumulate ? map[b, s] : 0) + weight * (1 / C) * sum_c (a[b, c, s] - b[b, c, s])^2, channels in ascending
+ * order.  a, b: [B, C, S] (S = the product of the spatial extents: 2-D and 3-D alike); map: [B, S], which may overlap
+ * neither input (refused).  A NaN input gives a NaN at its own pixel and nowhere else.  16-byte accesses when S % 4 == 0
+ * and every base is 16-byte aligned, a scalar path otherwise -- the same bits either way.  Launched after
+ * ddpm_clamp_mse_f32, which leaves the reconstruction clamped in place.                                                  */
+int ddpm_sqerr_map_f32(const float *a, const float *b, float *map, int B, int C, int64_t S, float weight, int accumulate,
+                       ddpm_stream_t stream);
+
 /* VQ-VAE quantiser (EMAQuantizer.quantize + embedding lookup, eval path; reached from
  * src/trainers/reconstruct.py:124,166 via vqvae.decode_stage_2_outputs): for every latent vector z = x[b, :, p],
  * idx[b, p] = argmin_k |z|^2 + |e_k|^2 - 2 z.e_k (first on ties) and out[b, :, p] = z + (e_idx - z).
@@ -422,6 +434,23 @@ int ddpm_maxpool3s2_f32(const float *in, float *out, int64_t planes, int H, int 
 /* One LPIPS layer: out[n] (+)= mean_hw( sum_c lin[c] * (f0[n,c]/(|f0[n,:]| + 1e-10) - f1[n,c]/(|f1[n,:]| + 1e-10))^2 ). */
 int ddpm_lpips_layer_f32(const float *f0, const float *f1, const float *lin, float *out, int N, int C, int HW,
                          int accumulate, ddpm_stream_t stream);
+
+/* Spatial LPIPS (anomaly maps).  The per-position value ddpm_lpips_layer_f32 averages away:
+ *   maps[n * row_stride + row_offset + p] = sum_c lin[c] * (f0[n,c,p]/(|f0[n,:,p]| + 1e-10) - f1[n,c,p]/(|f1[n,:,p]| + 1e-10))^2
+ * for p < HW; row_offset + HW <= row_stride, so the five layers of a pair land in one packed row [N, sum_k h_k w_k].  The
+ * kernel form depends on HW alone: a row's bits depend neither on N nor on its place in the batch.                        */
+int ddpm_lpips_layer_map_f32(const float *f0, const float *f1, const float *lin, float *maps, int N, int C, int HW,
+                             int64_t row_stride, int64_t row_offset, ddpm_stream_t stream);
+/* out[n, y, x] = (accumulate ? out[n, y, x] : 0) + weight * sum_{k < n_layers} bilinear_k(y + oy, x + ox): layer k's
+ * h_k x w_k map (layer k starts where layer k - 1 ends in the row of row_stride floats; extents of layers >= n_layers are
+ * ignored) resampled to Hfull x Wfull as nn.Upsample(size, mode="bilinear", align_corners=False) does:
+ *   sy = max((Y + 0.5) h / Hfull - 0.5, 0), y0 = min(floor(sy), h - 1), y1 = min(y0 + 1, h - 1), ly = sy - y0, x alike,
+ *   value = (1 - ly) ((1 - lx) m[y0,x0] + lx m[y0,x1]) + ly ((1 - lx) m[y1,x0] + lx m[y1,x1]),
+ * layers summed in ascending k in one launch.  out: [N, H, W], the window of the full grid at (oy, ox) (a 28-pixel image
+ * padded to 32 for LPIPS: oy = ox = 2, H = W = 28).  1 <= n_layers <= 5; extents 1 .. 4096.                                 */
+int ddpm_lpips_map_upsample_f32(const float *maps, float *out, int N, int64_t row_stride, int n_layers, int h0, int w0, int h1,
+                                int w1, int h2, int w2, int h3, int w3, int h4, int w4, int Hfull, int Wfull, int oy, int ox,
+                                int H, int W, float weight, int accumulate, ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Loss terms of VQ-VAE training (src/trainers/vqvae_trainer.py: 0.001 x PerceptualLoss + JukeboxLoss in the generator loss;

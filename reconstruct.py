@@ -59,6 +59,8 @@ _EXTENSIONS = [
     ("reset_scheduler_per_t", int, 0, "1: clear the PLMS history before each t-start (deviation, Q3)"),
     ("use_proj_attn", int, 0, "1: apply AttentionBlock.proj_attn (SURVEY A.3 open point)"),
     ("lpips_weights", None, None, "state_dict file with LPIPS-AlexNet weights"),
+    ("anomaly_maps", int, 0, "1: also write ood/maps_<name>.npz, the per-pixel LPIPS and squared-error maps averaged over the "
+                             "t-starts (2-D pixel-space models)"),
 ]
 
 
