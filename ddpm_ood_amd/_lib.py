@@ -149,6 +149,10 @@ SIGNATURES = {
     "ddpm_lpips_layer_map_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_int64, C.c_int64, C.c_void_p]),
     "ddpm_lpips_map_upsample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_int] * 17
                                     + [C.c_float, C.c_int, C.c_void_p]),
+    # ---- per-pixel Z-scores of the anomaly maps (additive: the ABI version stays)
+    "ddpm_map_stats_update_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ddpm_map_zscore_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p]),
+    "ddpm_map_blur_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
     "ddpm_lpips_layer_backward_f32":(C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
     "ddpm_maxpool3s2_backward_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_int] * 4 + [C.c_void_p]),
     "ddpm_lpips_conv1_dgrad_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p]),

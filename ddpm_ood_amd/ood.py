@@ -110,6 +110,51 @@ def main_likelihood(args, out_data=None):
     return dict(zip(out_data, scores))
 
 
+ZMAP_KEYS = ("z_mse_map", "z_lpips_map")
+ZMAP_REDUCTIONS = ("mean", "max")
+
+
+def score_zmaps(ind_npz, ood_npz, key: str = "z_mse_map", reduce: str = "mean"):
+    """AUROC of the per-pixel Z-maps (zmaps_*.npz of ``reconstruct.py --anomaly_z_maps 1``): an image's score is the mean, or
+    the maximum, of its Z-map ``key``; a repeated filename counts once, the first copy; in = 0, out = 1.  ``ind_npz`` /
+    ``ood_npz``: a path or the loaded mapping.  Returns (the table of both sets, AUROC)."""
+    if key not in ZMAP_KEYS:
+        raise ValueError(f"score_zmaps: key must be one of {ZMAP_KEYS}, got {key!r}")
+    if reduce not in ZMAP_REDUCTIONS:
+        raise ValueError(f"score_zmaps: reduce must be one of {ZMAP_REDUCTIONS}, got {reduce!r}")
+    frames = []
+    for src, kind in ((ind_npz, "in"), (ood_npz, "out")):
+        z = np.load(src) if isinstance(src, (str, Path)) else src
+        maps = np.asarray(z[key], dtype=np.float64)
+        flat = maps.reshape(maps.shape[0], -1)
+        df = pd.DataFrame({"filename": [str(f) for f in z["filename"]], "type": kind,
+                           "score": flat.mean(axis=1) if reduce == "mean" else flat.max(axis=1)})
+        frames.append(df[~df.duplicated(subset=["filename"])])
+    table = pd.concat(frames, ignore_index=True)
+    return table, roc_auc_score((table["type"] == "out").to_numpy().astype(int), table["score"].to_numpy())
+
+
+def main_zmaps(args, out_data=None):
+    """``ood_detection.py --score zmap``: the AUROC lines of ``main`` from zmaps_in.npz / zmaps_<name>.npz."""
+    model = args.model_name
+    run_dir = Path(args.output_dir) / model
+    print(f"Run directory: {str(run_dir)}")
+    out_dir = run_dir / "ood"
+    key, reduce = getattr(args, "zmap_key", "z_mse_map"), getattr(args, "zmap_reduce", "mean")
+    print(f"Score is the {reduce} of the per-pixel Z-map {key}")
+    if out_data is None:
+        out_data = out_datasets_for(model)
+    scores = []
+    for out_dataset in out_data:
+        df, auc = score_zmaps(out_dir / "zmaps_in.npz", out_dir / f"zmaps_{out_dataset}.npz", key, reduce)
+        print(f"n_in={(df['type'] == 'in').sum()} n_out={(df['type'] == 'out').sum()}")
+        scores.append(auc)
+    for o, s in zip(out_data, scores):
+        print(f"AUC for {model} vs {o}: {s * 100:.1f}")
+    print(f"Average AUC: {np.mean(scores) * 100:.1f}")
+    return dict(zip(out_data, scores))
+
+
 def main(args, out_data=None):
     model = args.model_name
     run_dir = Path(args.output_dir) / model

@@ -772,6 +772,96 @@ def sqerr_map(a, b, weight: float = 1.0, out=None):
     return out
 
 
+# ---- per-pixel Z-scores of the anomaly maps ------------------------------------------------------
+
+MAP_BLUR_MAX_RADIUS = 16  # kBlurMaxRadius of csrc/zmaps.hip
+
+
+def _fresh_out(out, shape, device, what):
+    """A fresh buffer, or the caller's own contiguous fp32 `out` of `shape` to write into."""
+    return _accumulator(out, shape, device, what)[0]
+
+
+def map_stats_update(values, n_prev: int, mean, m2):
+    """One batch merged into the running per-column statistics: ``values`` [B, *shape] (B rows of the validation set), ``mean`` and
+    ``m2`` (the sum of squared deviations) contiguous fp32 [*shape] on the device, updated in place; ``n_prev`` rows were merged
+    before (0: the buffers are written without being read).  Returns the new row count n_prev + B."""
+    lib = _lib.load()
+    values = require_device_f32(values, "values")
+    if values.ndim < 2 or values.shape[0] < 1:
+        raise ValueError(f"map_stats_update wants [B, *shape] values with B >= 1, got {tuple(values.shape)}")
+    B, shape = values.shape[0], tuple(values.shape[1:])
+    for name, t in (("mean", mean), ("m2", m2)):
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or tuple(t.shape) != shape or t.dtype != torch.float32
+                or not t.is_contiguous() or t.device != values.device):
+            raise ValueError(f"map_stats_update: {name} must be a contiguous float32 {shape} tensor on {values.device}")
+    if int(n_prev) < 0:
+        raise ValueError(f"map_stats_update: n_prev must not be negative, got {n_prev}")
+    check(lib.ddpm_map_stats_update_f32(ptr(values), B, int(np.prod(shape, dtype=np.int64)), int(n_prev), ptr(mean), ptr(m2),
+                                        stream_ptr()), "map_stats_update")
+    return int(n_prev) + B
+
+
+def map_zscore(values, mean, inv_std, weight: float = None, out=None):
+    """out[b, *shape] = weight * sum_t (values[b, t] - mean[t]) * inv_std[t] for ``values`` [B, n_t, *shape] and the tables
+    ``mean`` / ``inv_std`` [n_t, *shape]; ``weight`` defaults to 1 / n_t (the mean over the t-starts).  ``out``: a contiguous fp32
+    [B, *shape] to write into (it may overlap no input)."""
+    lib = _lib.load()
+    values = require_device_f32(values, "values")
+    mean = require_device_f32(mean, "mean")
+    inv_std = require_device_f32(inv_std, "inv_std")
+    if values.ndim < 3 or mean.shape != values.shape[1:] or inv_std.shape != mean.shape or min(values.shape[:2]) < 1:
+        raise ValueError(f"map_zscore wants values [B, n_t, *shape] and two tables [n_t, *shape], got {tuple(values.shape)}, "
+                         f"{tuple(mean.shape)} and {tuple(inv_std.shape)}")
+    B, n_t = values.shape[:2]
+    out = _fresh_out(out, (B,) + tuple(values.shape[2:]), values.device, "map_zscore")
+    w = 1.0 / n_t if weight is None else float(weight)
+    check(lib.ddpm_map_zscore_f32(ptr(values), ptr(mean), ptr(inv_std), ptr(out), B, n_t,
+                                  int(np.prod(values.shape[2:], dtype=np.int64)), w, stream_ptr()), "map_zscore")
+    return out
+
+
+def gaussian_taps(sigma: float, truncate: float = 4.0):
+    """The weights of ``scipy.ndimage.gaussian_filter`` (order 0) in float64: exp(-k^2 / 2 sigma^2) for |k| <= radius =
+    int(truncate * sigma + 0.5), normalised to sum 1.  sigma <= 0 or radius 0: the single weight 1."""
+    sigma = float(sigma)
+    radius = int(truncate * sigma + 0.5) if sigma > 0 else 0
+    if radius == 0:
+        return np.ones(1, dtype=np.float64)
+    k = np.arange(-radius, radius + 1, dtype=np.float64)
+    w = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+    return w / w.sum()
+
+
+def map_blur(maps, sigma: float = None, taps=None, out=None):
+    """Separable Gaussian smoothing of [N, H, W] maps with scipy's mode="reflect" boundary (``gaussian_filter(maps[n], sigma)``,
+    truncate 4).  ``taps``: the 2 radius + 1 weights as a device tensor (``gaussian_taps`` rounded to fp32) instead of ``sigma``,
+    for a caller that smooths many batches.  radius <= 16 (sigma < 4.125), else ValueError.  Not in place."""
+    lib = _lib.load()
+    maps = require_device_f32(maps, "maps")
+    if maps.ndim != 3 or min(maps.shape) < 1:
+        raise ValueError(f"map_blur wants [N, H, W] maps, got {tuple(maps.shape)}")
+    if (sigma is None) == (taps is None):
+        raise ValueError("map_blur: give sigma or taps (one of them)")
+    if taps is None:
+        if not float(sigma) >= 0.0 or int(4.0 * float(sigma) + 0.5) > MAP_BLUR_MAX_RADIUS:
+            raise ValueError(f"map_blur: sigma = {sigma} needs radius {int(4.0 * float(sigma) + 0.5) if sigma == sigma else sigma}, "
+                             f"outside 0 .. {MAP_BLUR_MAX_RADIUS}")
+        w = gaussian_taps(sigma)
+        taps = torch.empty((len(w),), dtype=torch.float32, device=maps.device)
+        taps.copy_(torch.from_numpy(w.astype(np.float32)))
+    else:
+        taps = require_device_f32(taps, "taps")
+        if taps.ndim != 1 or taps.numel() % 2 != 1:
+            raise ValueError(f"map_blur: taps must be an odd number of weights in one row, got {tuple(taps.shape)}")
+        if taps.numel() > 2 * MAP_BLUR_MAX_RADIUS + 1:
+            raise ValueError(f"map_blur: radius {taps.numel() // 2} is above the maximum of {MAP_BLUR_MAX_RADIUS}")
+    N, H, W = maps.shape
+    out = _fresh_out(out, (N, H, W), maps.device, "map_blur")
+    check(lib.ddpm_map_blur_f32(ptr(maps), ptr(out), ptr(taps), taps.numel() // 2, N, H, W, stream_ptr()), "map_blur")
+    return out
+
+
 # ---- LPIPS-AlexNet pieces (src/losses/perceptual_loss.py:105-186) -------------------------------------
 
 def lpips_conv(x, weight, bias, stride: int, pad: int, relu: bool = True, in_scale=None, in_shift=None):

@@ -173,11 +173,13 @@ class LPIPS(nn.Module):
         return [s1, s2, s3, s3, s3]
 
     def _forward_hip(self, in0, in1, normalize: bool, value: bool = True, spatial: bool = False, window=None, weight: float = 1.0,
-                     out=None):
+                     out=None, second_weight=None):
         """(value [N, 1, 1, 1] or None, map [N, 1, H, W] or None) from ONE feature pass.  The value comes from the same
         lpips_layer calls whether or not the map is asked for.  Map: every layer's per-position distance into one packed
         row per pair, then one launch that resamples the five layers to the input's extent (``window`` = (oy, ox, H, W) of
-        it) and sums them, times ``weight``, into ``out`` [N, H, W] if given."""
+        it) and sums them, times ``weight``, into ``out`` [N, H, W] if given.  ``second_weight`` given: a third result, the
+        same packed rows resampled once more, times ``second_weight``, into a fresh [N, 1, H, W] (a second launch of the
+        resampling kernel after the first; nothing before it changes)."""
         from . import ops
 
         n = in0.shape[0]
@@ -202,6 +204,9 @@ class LPIPS(nn.Module):
                 offset += f.shape[2] * f.shape[3]
         if spatial:
             full_map = ops.lpips_map_upsample(maps, sizes, full, window, weight, out)
+            if second_weight is not None:
+                second = ops.lpips_map_upsample(maps, sizes, full, window, second_weight)
+                return (val.reshape(n, 1, 1, 1) if value else None), full_map[:, None], second[:, None]
             maps = full_map[:, None]
         return (val.reshape(n, 1, 1, 1) if value else None), maps
 
@@ -218,13 +223,14 @@ class LPIPS(nn.Module):
         val, amap = self._forward_hip(in0.float(), in1.float(), normalize, value=not self.spatial, spatial=self.spatial)
         return amap if self.spatial else val
 
-    def forward_with_map(self, in0, in1, normalize: bool = False, window=None, weight: float = 1.0, out=None):
+    def forward_with_map(self, in0, in1, normalize: bool = False, window=None, weight: float = 1.0, out=None, second_weight=None):
         """(value [N, 1, 1, 1], map [N, 1, H, W]) from one feature pass: the value carries the bits of ``forward`` with
         spatial=False.  ``window`` = (oy, ox, H, W) crops the map (an image that was padded for LPIPS); ``out`` [N, H, W]:
-        the map is added into it, times ``weight``, instead of returned fresh."""
+        the map is added into it, times ``weight``, instead of returned fresh.  ``second_weight`` given: (value, map, a fresh
+        second map times ``second_weight``) -- the per-t maps of --anomaly_z_maps beside the accumulated one."""
         self._check(in0, in1)
         return self._forward_hip(in0.float(), in1.float(), normalize, value=True, spatial=True, window=window, weight=weight,
-                                 out=out)
+                                 out=out, second_weight=second_weight)
 
 
 class PerceptualLoss(nn.Module):
@@ -268,14 +274,16 @@ class PerceptualLoss(nn.Module):
         return self.perceptual_function.forward(y, y_pred, normalize=self.lpips_normalize) * self.perceptual_factor
 
     @torch.no_grad()
-    def forward_with_map(self, y: torch.Tensor, y_pred: torch.Tensor, window=None, weight: float = 1.0, out=None):
+    def forward_with_map(self, y: torch.Tensor, y_pred: torch.Tensor, window=None, weight: float = 1.0, out=None,
+                         second_weight=None):
         """2-D only: (the loss ``forward`` returns without ``spatial``, bit for bit; its per-pixel map [N, 1, H, W]) from one
-        feature pass -- ``LPIPS.forward_with_map`` has the arguments."""
+        feature pass -- ``LPIPS.forward_with_map`` has the arguments (``second_weight`` given: a second map comes third)."""
         if self.dimensions != 2:
             raise NotImplementedError("Perceptual maps are built for 2D inputs only.")
-        val, amap = self.perceptual_function.forward_with_map(y.float(), y_pred.float(), normalize=self.lpips_normalize,
-                                                              window=window, weight=weight, out=out)
-        return val * self.perceptual_factor, amap
+        val, *maps = self.perceptual_function.forward_with_map(y.float(), y_pred.float(), normalize=self.lpips_normalize,
+                                                               window=window, weight=weight, out=out,
+                                                               second_weight=second_weight)
+        return (val * self.perceptual_factor, *maps)
 
     def _calculate_fake_3d_loss(self, y, y_pred, permute_dims, view_dims):
         ys = y.permute(*permute_dims).contiguous().view(-1, *(y.shape[d] for d in view_dims))

@@ -32,7 +32,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import _lib, ops, zmaps
 from .data import get_data_loader
 from .perceptual import PerceptualLoss
 from .scheduler import DDPMScheduler, PNDMScheduler
@@ -334,10 +334,21 @@ class Reconstruct(BaseTrainer):
         if self.anomaly_maps and (int(args.spatial_dimension) != 2 or args.vqvae_checkpoint):
             raise ValueError("--anomaly_maps 1: anomaly maps cover 2-D pixel-space models only (no --spatial_dimension 3, no "
                              "--vqvae_checkpoint): 2.5-D and latent maps are not built")
+        # --anomaly_z_maps 1 (extension): the per-t maps normalised per pixel by the validation set's mean and
+        # standard deviation, averaged over the t-starts (ood/map_stats.npz, ood/zmaps_<name>.npz).  Off without the attribute.
+        self.anomaly_z_maps = bool(getattr(args, "anomaly_z_maps", 0))
+        self.z_sigma = float(getattr(args, "anomaly_z_sigma", 0.0) or 0.0)
+        self.z_std_floor = float(getattr(args, "anomaly_z_std_floor", 0.01))
+        if self.anomaly_z_maps:
+            zmaps.check_flags(args.spatial_dimension, args.vqvae_checkpoint, self.z_sigma, self.z_std_floor)
         super().__init__(args)
         if not self.found_checkpoint:
             raise FileNotFoundError("Failed to find a saved model checkpoint.")
         self.last_maps = None  # the maps of the last get_scores call (rank 0, --anomaly_maps 1), what _write puts into the .npz
+        self.last_zmaps = None  # the same for --anomaly_z_maps 1 (the in / out sets)
+        self.last_map_stats = None  # (MapStats, t values) of the last validation pass, merged over the ranks
+        self._z_tables = None  # (t values, mean, inv_std on the device) the in / out passes normalise by
+        self._z_taps = None  # the smoothing weights on the device (--anomaly_z_sigma > 0)
         self.out_dir = self.run_dir / "ood"
         if self.rank == 0:
             self.out_dir.mkdir(exist_ok=True)
@@ -414,8 +425,11 @@ class Reconstruct(BaseTrainer):
             print(f"{dataset_name}")
         pl = self._perceptual()
         self.model.eval()
-        ids_all, names_all, scores_all, maps_all = [], [], [], []
-        self.last_maps = None
+        ids_all, names_all, scores_all, maps_all, zmaps_all = [], [], [], [], []
+        self.last_maps = self.last_zmaps = None
+        # --anomaly_z_maps 1: the validation pass accumulates the per-pixel statistics, every other pass is normalised by them
+        z_stats = zmaps.MapStats() if self.anomaly_z_maps and dataset_name == "val" else None
+        z_skipped = 0
         t_values = [int(t) for t in reversed(self.make_scheduler().timesteps)[1::inference_skip_factor]
                     if (self.max_t_start is None or int(t) <= int(self.max_t_start))
                     and (self.t_start_subset is None or int(t) in set(self.t_start_subset))]
@@ -427,7 +441,7 @@ class Reconstruct(BaseTrainer):
             guard["vq_near_ties"] = 0  # latent positions whose two nearest codes were within 1e-5: candidates for a code flip
             _lib.vq_near_ties_read(clear=True)
         for batch in loader:
-            scores, t_values, n_r, n_f, B, dt, maps = self._score_batch(batch, pl, inference_skip_factor)
+            scores, t_values, n_r, n_f, B, dt, maps, per_t_maps = self._score_batch(batch, pl, inference_skip_factor)
             # numeric guard (include/ddpm_ood_hip.h): a non-finite eps / reconstruction / latent set the device status word.
             # With the split-f16 kernels on, that may be an operand beyond the f16 range rather than a genuine fp32
             # overflow: run the affected IMAGES again on the fp32-MFMA kernels; what is still non-finite then is written as
@@ -450,10 +464,12 @@ class Reconstruct(BaseTrainer):
                 prev = _lib.set_split_f16(False)
                 try:
                     sub = sub_batch(batch, bad)
-                    scores_b, t_values, _, n_f2, _, dt2, maps_b = self._score_batch(sub, pl, inference_skip_factor)
+                    scores_b, t_values, _, n_f2, _, dt2, maps_b, per_t_b = self._score_batch(sub, pl, inference_skip_factor)
                     scores[torch.as_tensor(bad, device=scores.device)] = scores_b
                     if maps is not None:  # the maps follow the scores that are kept
                         maps[torch.as_tensor(bad, device=maps.device)] = maps_b
+                    if per_t_maps is not None:
+                        per_t_maps[torch.as_tensor(bad, device=per_t_maps.device)] = per_t_b
                     n_f += n_f2
                     dt += dt2
                     word = _lib.status_read(clear=True)
@@ -473,6 +489,8 @@ class Reconstruct(BaseTrainer):
             scores_all.append(scores)
             if maps is not None:
                 maps_all.append(maps.cpu())  # one device->host copy per batch, after the batch's synchronisation
+            if per_t_maps is not None:  # after the guard: the statistics see the per-t maps of the scores that are kept
+                z_skipped += self._z_batch(z_stats, scores, per_t_maps, t_values, zmaps_all)
             ids_all.append(torch.tensor(batch["index"], dtype=torch.int32))
             names_all.extend(batch["image_meta_dict"]["filename_or_obj"])
             if quiet:
@@ -483,13 +501,18 @@ class Reconstruct(BaseTrainer):
                 print(f"Took {dt}s for a batch size of {B}")
         self.last_stats = {"reconstructions": n_recon, "unet_forwards": n_fwd,
                            "lpips_pretrained": bool(pl.perceptual_function.pretrained), **guard}
-        return self._collect(loader, dataset_name, t_values, ids_all, names_all, scores_all, quiet, maps_all)
+        if self.anomaly_z_maps:
+            self.last_stats["zmap_rows_skipped"] = z_skipped
+            if z_stats is not None:
+                self._z_finish_validation(loader, z_stats, t_values)
+        return self._collect(loader, dataset_name, t_values, ids_all, names_all, scores_all, quiet, maps_all, zmaps_all)
 
     def _score_batch(self, batch, pl, inference_skip_factor):
         """One batch through reconstruct.py:97-204: every t-start's noise, PLMS trajectory, decode, MSE and LPIPS.
-        Returns (scores [B, n_t, 2] on the device, t values, reconstructions, UNet image-forwards, B, seconds, maps): maps is
-        None, or with --anomaly_maps 1 the device tensor [B, 2, H, W] of the per-pixel LPIPS (channel 0) and squared error
-        (channel 1), each the mean over the t-starts."""
+        Returns (scores [B, n_t, 2] on the device, t values, reconstructions, UNet image-forwards, B, seconds, maps, per-t
+        maps): maps is None, or with --anomaly_maps 1 the device tensor [B, 2, H, W] of the per-pixel LPIPS (channel 0) and
+        squared error (channel 1), each the mean over the t-starts; per-t maps is None, or with --anomaly_z_maps 1 the same two
+        channels of every t-start by itself, [B, n_t, 2, H, W] (B * n_t * 2 * H * W * 4 bytes)."""
         n_recon = n_fwd = 0
         sched = self.make_scheduler()  # one per batch: PLMS history leaks across t-starts (Q3)
         timesteps = sched.timesteps
@@ -513,6 +536,7 @@ class Reconstruct(BaseTrainer):
             lp_map = torch.zeros((B,) + tuple(images_original.shape[2:]), dtype=torch.float32, device=self.device)
             se_map = torch.zeros_like(lp_map)
             w_t = 1.0 / max(len(t_values), 1)
+        per_t_maps = [] if self.anomaly_z_maps else None  # fresh maps of every t-start at weight 1 (2-D only)
         for t_start in start_points:
             if self.reset_scheduler_per_t:
                 sched.set_timesteps(self.num_inference_steps)
@@ -545,12 +569,25 @@ class Reconstruct(BaseTrainer):
             mse = ops.clamp_mse_(images_original, x, self.b_scale)  # x / b_scale, clamp_(0, 1), MSE
             if self.anomaly_maps:  # (2-D only) the same value from the same launches, and the map from the same features
                 ops.sqerr_map(images_original, x, w_t, out=se_map)
+                # --anomaly_z_maps 1 beside it: the resampling kernel runs a second time on the same packed layer maps
+                second = {"second_weight": 1.0} if self.anomaly_z_maps else {}
                 if images_original.shape[3] == 28:
-                    pd_, _ = pl.forward_with_map(F.pad(images_original, (2, 2, 2, 2)), F.pad(x, (2, 2, 2, 2)),
-                                                 window=(2, 2) + tuple(images_original.shape[2:]), weight=w_t, out=lp_map)
+                    pd_, *lp_t = pl.forward_with_map(F.pad(images_original, (2, 2, 2, 2)), F.pad(x, (2, 2, 2, 2)),
+                                                     window=(2, 2) + tuple(images_original.shape[2:]), weight=w_t, out=lp_map,
+                                                     **second)
                 else:
-                    pd_, _ = pl.forward_with_map(images_original, x, weight=w_t, out=lp_map)
+                    pd_, *lp_t = pl.forward_with_map(images_original, x, weight=w_t, out=lp_map, **second)
                 pd_ = pd_.reshape(B)
+                if self.anomaly_z_maps:
+                    per_t_maps.append(torch.stack([lp_t[1][:, 0], ops.sqerr_map(images_original, x)], dim=1))
+            elif self.anomaly_z_maps:  # (2-D only) the score from the launches ``pl(...)`` makes, and this t-start's two maps
+                if images_original.shape[3] == 28:
+                    pd_, lp_t = pl.forward_with_map(F.pad(images_original, (2, 2, 2, 2)), F.pad(x, (2, 2, 2, 2)),
+                                                    window=(2, 2) + tuple(images_original.shape[2:]))
+                else:
+                    pd_, lp_t = pl.forward_with_map(images_original, x)
+                pd_ = pd_.reshape(B)
+                per_t_maps.append(torch.stack([lp_t[:, 0], ops.sqerr_map(images_original, x)], dim=1))
             elif self.spatial_dimension == 2:
                 if images_original.shape[3] == 28:
                     pd_ = pl(F.pad(images_original, (2, 2, 2, 2)), F.pad(x, (2, 2, 2, 2)))
@@ -564,13 +601,85 @@ class Reconstruct(BaseTrainer):
             n_recon += B
         scores = torch.stack(per_t, dim=1)  # [B, n_t, 2] on the device
         maps = torch.stack([lp_map, se_map], dim=1) if self.anomaly_maps else None  # [B, 2, H, W]
+        if per_t_maps is not None:
+            per_t_maps = torch.stack(per_t_maps, dim=1) if per_t_maps else None  # [B, n_t, 2, H, W] (no t-start: nothing)
         torch.cuda.current_stream().synchronize()
         t2 = time.time()
-        return scores, t_values, n_recon, n_fwd, B, t2 - t1, maps
+        return scores, t_values, n_recon, n_fwd, B, t2 - t1, maps, per_t_maps
 
-    def _collect(self, loader, dataset_name, t_values, ids_all, names_all, scores_all, quiet, maps_all=()):
+    def _z_batch(self, z_stats, scores, per_t_maps, t_values, zmaps_all):
+        """--anomaly_z_maps 1, one batch after the numeric guard.  Validation pass (``z_stats`` given): the per-t maps of the
+        images whose scores are all finite go into the running statistics (one launch); returns how many images were left out.
+        Any other pass: the batch's Z-maps [B, 2, H, W] -- one launch, one more per batch when smoothing -- are appended to
+        ``zmaps_all`` on the host (one device->host copy per batch, after the batch's synchronisation)."""
+        B, n_t = per_t_maps.shape[:2]
+        if z_stats is not None:
+            finite = torch.isfinite(scores).all(dim=2).all(dim=1)
+            keep = int(finite.sum())
+            if keep == B:
+                z_stats.update(per_t_maps)
+            elif keep:
+                z_stats.update(per_t_maps[finite].contiguous())
+            return B - keep
+        if self._z_tables is None or self._z_tables[0] != list(t_values) or self._z_tables[1].shape != per_t_maps.shape[1:]:
+            self._z_tables = self._z_load_tables(t_values, tuple(per_t_maps.shape[3:]))
+        _, mean, inv_std = self._z_tables
+        H, W = per_t_maps.shape[3:]
+        z = ops.map_zscore(per_t_maps.reshape(B, n_t, 2 * H * W), mean.reshape(n_t, 2 * H * W), inv_std.reshape(n_t, 2 * H * W))
+        if self.z_sigma > 0:
+            if self._z_taps is None:
+                self._z_taps = torch.from_numpy(ops.gaussian_taps(self.z_sigma).astype(np.float32)).to(self.device)
+            z = ops.map_blur(z.reshape(B * 2, H, W), taps=self._z_taps)
+        zmaps_all.append(z.reshape(B, 2, H, W).cpu())
+        return 0
+
+    def _z_set_tables(self, stats, t_values):
+        mean, inv_std = stats.finalize(self.z_std_floor)
+        self._z_tables = ([int(t) for t in t_values], torch.from_numpy(mean).to(self.device), torch.from_numpy(inv_std).to(self.device))
+        return self._z_tables
+
+    def _z_load_tables(self, t_values, extent):
+        """The statistics of this process's validation pass, else those of ood/map_stats.npz (--run_val 0)."""
+        if self.last_map_stats is not None:
+            stats, t_val = self.last_map_stats
+            if [int(t) for t in t_val] != [int(t) for t in t_values] or tuple(stats.tables()[1].shape[2:]) != tuple(extent):
+                raise ValueError(f"--anomaly_z_maps 1: the validation pass gave statistics for t = {t_val} and maps of "
+                                 f"{tuple(stats.tables()[1].shape[2:])}, this set has t = {list(t_values)} and {tuple(extent)}")
+            return self._z_set_tables(stats, t_values)
+        return self._z_set_tables(zmaps.MapStats.load(self.out_dir / zmaps.STATS_FILE, t_values, extent), t_values)
+
+    def _z_finish_validation(self, loader, z_stats, t_values):
+        """After the validation pass: with N ranks ONE all_gather of (n, mean, m2) and the same float64 merge on every rank,
+        so that every rank finalises the same tables; rank 0 keeps them for ``_write`` (ood/map_stats.npz)."""
+        n, mean, m2 = z_stats.tables()
+        if self.ddp:
+            if hasattr(loader, "all_names") and len(loader.all_names) < self.world:
+                raise ValueError(f"--anomaly_z_maps 1: {len(loader.all_names)} images over {self.world} ranks leave a rank "
+                                 f"without an image, and the maps' extent comes from the images")
+            if mean is None:
+                raise ValueError("--anomaly_z_maps 1: this rank counted no validation image: no statistics to gather")
+            if n >= 1 << 24:
+                raise ValueError(f"--anomaly_z_maps 1: a row count of {n} is not exact in the fp32 payload")
+            payload = torch.cat([torch.tensor([float(n)], dtype=torch.float32, device=self.device),
+                                 z_stats.mean.reshape(-1), z_stats.m2.reshape(-1)])[None]  # [1, 1 + 2 P]: stacked rank by rank
+            if dist.get_backend() == "gloo" and payload.is_cuda:  # (the test hook of gather_scores)
+                payload = payload.cpu()
+            out = torch.empty((self.world, payload.numel()), dtype=torch.float32, device=payload.device)
+            dist.all_gather_into_tensor(out, payload)
+            out = out.cpu().double().numpy()
+            P = mean.size
+            n, mean, m2 = zmaps.MapStats.merge([(int(r[0]), r[1:1 + P].reshape(mean.shape), r[1 + P:].reshape(mean.shape))
+                                                for r in out])
+        if mean is None:
+            raise ValueError("--anomaly_z_maps 1: the validation pass counted no image: no statistics")
+        stats = zmaps.MapStats.from_tables(n, mean, m2, t_values)
+        self.last_map_stats = (stats, [int(t) for t in t_values])
+        self._z_set_tables(stats, t_values)  # (n < 2 or a channel that never varies: refused here, on every rank alike)
+
+    def _collect(self, loader, dataset_name, t_values, ids_all, names_all, scores_all, quiet, maps_all=(), zmaps_all=()):
         """reconstruct.py:238-250: everyone's rows on every rank, through ONE collective (with --anomaly_maps 1 a second one
-        of the same scheme carries the maps; rank 0 keeps them in ``last_maps`` for ``_write``)."""
+        of the same scheme carries the maps; rank 0 keeps them in ``last_maps`` for ``_write``; --anomaly_z_maps 1: a further
+        one for the Z-maps of an in / out set, ``last_zmaps``)."""
         if not scores_all and not self.ddp:
             return []
         local_ids = torch.cat(ids_all) if ids_all else torch.zeros((0,), dtype=torch.int32)
@@ -601,16 +710,32 @@ class Reconstruct(BaseTrainer):
                                    loader.batch_size, dataset_name)
         if self.anomaly_maps:
             self._collect_maps(loader, results, t_values, local_ids, ids.cpu().tolist(), name_of, maps_all)
+        if self.anomaly_z_maps and dataset_name != "val":  # (the validation set gets no Z-maps)
+            got = self._gather_map_rows("--anomaly_z_maps 1", loader, results, local_ids, ids.cpu().tolist(), name_of, zmaps_all)
+            if got is not None:
+                stems, z = got
+                self.last_zmaps = {"filename": np.asarray(stems), "t": np.asarray(t_values, dtype=np.int64),
+                                   "z_lpips_map": np.ascontiguousarray(z[:, 0]), "z_mse_map": np.ascontiguousarray(z[:, 1]),
+                                   "sigma": np.float64(self.z_sigma), "rel_floor": np.float64(self.z_std_floor)}
         return results
 
     def _collect_maps(self, loader, results, t_values, local_ids, gathered_ids, name_of, maps_all):
         """The maps of every rank's images in the CSV's order of first appearance (rank 0 keeps them: ``last_maps``)."""
+        got = self._gather_map_rows("--anomaly_maps 1", loader, results, local_ids, gathered_ids, name_of, maps_all)
+        if got is not None:
+            stems, maps = got
+            self.last_maps = {"filename": np.asarray(stems), "t": np.asarray(t_values, dtype=np.int64),
+                              "lpips_map": np.ascontiguousarray(maps[:, 0]), "mse_map": np.ascontiguousarray(maps[:, 1])}
+
+    def _gather_map_rows(self, flag, loader, results, local_ids, gathered_ids, name_of, maps_all):
+        """Per-image rows [n, 2, H, W] of every rank, in the CSV's order of first appearance: (filenames, rows) on rank 0,
+        None on the others."""
         if self.ddp and hasattr(loader, "all_names") and len(loader.all_names) < self.world:
             # (every rank sees the same list and raises alike: a rank without an image does not know the maps' extent)
-            raise ValueError(f"--anomaly_maps 1: {len(loader.all_names)} images over {self.world} ranks leave a rank without "
+            raise ValueError(f"{flag}: {len(loader.all_names)} images over {self.world} ranks leave a rank without "
                              f"an image, and the maps' extent comes from the images")
         if not maps_all:
-            raise ValueError("--anomaly_maps 1: this rank scored no batch (--drop_last on a short shard?): no maps to gather")
+            raise ValueError(f"{flag}: this rank scored no batch (--drop_last on a short shard?): no maps to gather")
         maps = torch.cat(list(maps_all), dim=0)
         map_ids = gathered_ids
         if self.ddp:
@@ -619,18 +744,22 @@ class Reconstruct(BaseTrainer):
             gids, maps, _ = gather_rows(local_ids.to(self.device), maps.to(self.device), n_max)
             map_ids, maps = gids.cpu().tolist(), maps.cpu()
         if self.rank != 0:
-            return
+            return None
         stems, picks = map_rows_in_csv_order(results, map_ids, name_of)
-        maps = maps[torch.as_tensor(picks, dtype=torch.long)].numpy()
-        self.last_maps = {"filename": np.asarray(stems), "t": np.asarray(t_values, dtype=np.int64),
-                          "lpips_map": np.ascontiguousarray(maps[:, 0]), "mse_map": np.ascontiguousarray(maps[:, 1])}
+        return stems, maps[torch.as_tensor(picks, dtype=torch.long)].numpy()
 
     def _write(self, results_list, name):
         if self.rank == 0:
             pd.DataFrame(results_list).to_csv(self.out_dir / f"results_{name}.csv")
             if self.anomaly_maps and self.last_maps is not None:  # filename [N], t [n_t], lpips_map / mse_map fp32 [N, H, W]
                 np.savez(self.out_dir / f"maps_{name}.npz", **self.last_maps)
-        self.last_maps = None
+            if self.anomaly_z_maps and name == "val" and self.last_map_stats is not None:
+                # t [n_t], n, mean / std fp32 [n_t, 2, H, W] (the un-floored std), channels, rel_floor
+                self.last_map_stats[0].save(self.out_dir / zmaps.STATS_FILE, self.last_map_stats[1], self.z_std_floor)
+            if self.anomaly_z_maps and self.last_zmaps is not None:
+                # filename [N], t [n_t], z_lpips_map / z_mse_map fp32 [N, H, W], sigma, rel_floor
+                np.savez(self.out_dir / f"zmaps_{name}.npz", **self.last_zmaps)
+        self.last_maps = self.last_zmaps = None
 
     def reconstruct(self, args):
         if bool(args.run_val):

@@ -453,6 +453,33 @@ int ddpm_lpips_map_upsample_f32(const float *maps, float *out, int N, int64_t ro
                                 int H, int W, float weight, int accumulate, ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Per-pixel Z-scores of the anomaly maps against the validation set (--anomaly_z_maps 1).  Entry points added
+ * without an ABI bump; no workspace, no size function; every pointer but the stream is a device buffer.  Each output value is
+ * one fixed sequence of fp32 operations (no atomics, no reduction across threads).  The first two use 16-byte accesses when
+ * the row length is a multiple of 4 and every base is 16-byte aligned, a scalar path otherwise -- the same bits either way.
+ * ---------------------------------------------------------------------------------- */
+/* Running per-column mean and sum of squared deviations (Chan's update), one batch per call.  values: [B, P]; mean, m2: [P];
+ * n_prev: the rows merged so far (the same for every column).  Per column j, b ascending:
+ *   mb = (sum_b v[b, j]) / B;   Mb = sum_b (v[b, j] - mb)^2   (a second pass);
+ *   n_prev == 0: mean = mb, m2 = Mb -- the buffers' previous contents are not read;
+ *   else delta = mb - mean, mean = mean + delta * (B / n), m2 = m2 + (Mb + (delta * delta) * (n_prev * B / n)), n = n_prev + B.
+ * The two ratios are formed on the host in float64 by this entry point and handed to the kernel as fp32 scalars.  Rows that
+ * are not to be counted (non-finite ones) are the caller's business.  No operand may overlap another (refused).            */
+int ddpm_map_stats_update_f32(const float *values, int B, int64_t P, int64_t n_prev, float *mean, float *m2,
+                              ddpm_stream_t stream);
+/* out[b, p] = weight * sum_t (values[b, t, p] - mean[t, p]) * inv_std[t, p], t ascending (the sum starts with its first
+ * addend).  values: [B, n_t, P1]; mean, inv_std: [n_t, P1]; out: [B, P1], written, and refused if it overlaps an input.  A
+ * row's bits depend neither on B nor on its place in the batch; a NaN stays at its own pixel.                             */
+int ddpm_map_zscore_f32(const float *values, const float *mean, const float *inv_std, float *out, int B, int n_t, int64_t P1,
+                        float weight, ddpm_stream_t stream);
+/* Separable smoothing of [N, H, W] maps with the 2 radius + 1 weights of taps (a device buffer), scipy.ndimage's
+ * mode="reflect" boundary:  tmp[y, x] = sum_k taps[k] in[refl(y + k - radius, H), x], then out[y, x] = sum_k taps[k]
+ * tmp[y, refl(x + k - radius, W)], k ascending, each sum starting with its first product;  refl(i, L): m = i mod 2L (not
+ * negative), m < L ? m : 2L - 1 - m -- any radius up to the maximum of 16, also beyond H or W (H or W = 1 included).  One
+ * launch; radius 0 with taps[0] = 1 is an exact copy; out may overlap neither in nor taps (refused: not in place).        */
+int ddpm_map_blur_f32(const float *in, float *out, const float *taps, int radius, int N, int H, int W, ddpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Loss terms of VQ-VAE training (src/trainers/vqvae_trainer.py: 0.001 x PerceptualLoss + JukeboxLoss in the generator loss;
  * SURVEY.md A.8).  Entry points added without an ABI bump.  Everything is deterministic (fixed-order sums, no atomics).
  * ---------------------------------------------------------------------------------- */

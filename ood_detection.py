@@ -17,8 +17,11 @@ def parse_args(argv=None):
                    help="extension: which Z-score feeds the AUROC (the reference hard-codes mse)")
     p.add_argument("--out_data", default=None,
                    help="extension: comma list of OOD set names (default: picked from --model_name)")
-    p.add_argument("--score", default="reconstruction", choices=["reconstruction", "likelihood"],
-                   help="extension: likelihood reads the likelihood_*.csv files of likelihood.py and ranks by NLL")
+    p.add_argument("--score", default="reconstruction", choices=["reconstruction", "likelihood", "zmap"],
+                   help="extension: likelihood reads the likelihood_*.csv files of likelihood.py and ranks by NLL; zmap reads the "
+                        "zmaps_*.npz files of reconstruct.py --anomaly_z_maps 1 and ranks by a reduction of the per-pixel Z-map")
+    p.add_argument("--zmap_key", default="z_mse_map", choices=["z_mse_map", "z_lpips_map"], help="--score zmap: which Z-map")
+    p.add_argument("--zmap_reduce", default="mean", choices=["mean", "max"], help="--score zmap: mean or maximum over the pixels")
     return p.parse_args(argv)
 
 
@@ -29,5 +32,5 @@ if __name__ == "__main__":
 
     for model in args.model_name.split(","):
         args.model_name = model
-        run = ood.main_likelihood if args.score == "likelihood" else ood.main
+        run = {"likelihood": ood.main_likelihood, "zmap": ood.main_zmaps}.get(args.score, ood.main)
         run(args, out_data=args.out_data.split(",") if args.out_data else None)

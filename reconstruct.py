@@ -61,6 +61,11 @@ _EXTENSIONS = [
     ("lpips_weights", None, None, "state_dict file with LPIPS-AlexNet weights"),
     ("anomaly_maps", int, 0, "1: also write ood/maps_<name>.npz, the per-pixel LPIPS and squared-error maps averaged over the "
                              "t-starts (2-D pixel-space models)"),
+    ("anomaly_z_maps", int, 0, "1: also write ood/map_stats.npz (per-pixel mean and std of every t-start's maps over the "
+                               "validation set) and ood/zmaps_<name>.npz, the in / out sets' maps as Z-scores against them, "
+                               "averaged over the t-starts (2-D pixel-space models)"),
+    ("anomaly_z_sigma", float, 0.0, "Gaussian smoothing of the Z-maps in pixels (0: none; below 4.125)"),
+    ("anomaly_z_std_floor", float, 0.01, "a pixel's std is floored at this fraction of the largest std of its (t, channel)"),
 ]
 
 
