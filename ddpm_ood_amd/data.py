@@ -19,7 +19,8 @@ non-interlaced) and binary PGM / PPM, with PILReader's axis swap -- JPEG / TIFF 
 
 Synthetic id specs (no dataset can be downloaded here):
     synthetic:<kind>[:n=N][:size=S][:channels=C][:seed=K][:mix=P][:name=X]
-        kind in {blobs, noise, speckle (blobs + P % uniform noise), blobs3d, noise3d}
+        kind in {blobs, noise, speckle (blobs + P % uniform noise), lesion (blobs with one disc of uniform noise, P % of the
+                 extent across; the disc is the ground-truth mask: ``synthetic_masks``), blobs3d, noise3d}
 3-D volumes ([N, C, D, H, W]; ``.npy`` files of shape (D, H, W) or (C, D, H, W)) are handled with the
 same transforms (crop, area resize, min-max scale, flips of the first / second spatial axis).
 """
@@ -67,9 +68,46 @@ def _blobs3d(n: int, channels: int, size: int, gen: torch.Generator) -> torch.Te
     return out
 
 
+def lesion_radius(size: int, mix: int) -> float:
+    """Radius of the disc of kind "lesion": its diameter is ``mix`` percent of the extent, the radius at least 2 pixels."""
+    return max(2.0, mix / 100.0 * size / 2.0)
+
+
+def _lesion(n: int, channels: int, size: int, seed: int, mix: int):
+    """(images, masks uint8 [N, 1, H, W]) of kind "lesion": the min-max-scaled blobs of the same seed with one disc per image
+    replaced by uniform noise.  The centres and then the noise are drawn from the same generator after the blobs; a centre lies
+    in [r, size - 1 - r] on both axes, so that the disc (y - cy)^2 + (x - cx)^2 <= r^2 lies inside the image.  Nothing is
+    rescaled afterwards: outside the disc the image is ``scale_intensity(_blobs(...))`` bit for bit."""
+    gen = torch.Generator().manual_seed(seed)
+    x = scale_intensity(_blobs(n, channels, size, gen))
+    r = lesion_radius(size, mix)
+    centres = r + torch.rand(n, 2, generator=gen) * max(size - 1 - 2 * r, 0.0)
+    if size - 1 < 2 * r:  # (a disc wider than the image: centred, cut by the border)
+        centres = torch.full((n, 2), (size - 1) / 2.0)
+    noise = torch.rand(n, channels, size, size, generator=gen)
+    ys, xs = torch.meshgrid(torch.arange(size, dtype=torch.float32), torch.arange(size, dtype=torch.float32), indexing="ij")
+    inside = ((ys[None] - centres[:, 0, None, None]) ** 2 + (xs[None] - centres[:, 1, None, None]) ** 2 <= r * r)[:, None]
+    return torch.where(inside, noise, x), inside.to(torch.uint8)
+
+
+def synthetic_masks(kind: str, n: int, channels: int = 1, size: int = 32, seed: int = 0, mix: int = 10) -> torch.Tensor:
+    """The ground-truth anomaly masks of ``synthetic_images`` with the same arguments: uint8 [N, 1, *spatial], 1 inside the disc
+    of kind "lesion", all zero for every other kind."""
+    if kind == "lesion":
+        return _lesion(n, channels, size, seed, mix)[1]
+    if kind in ("blobs3d", "noise3d"):
+        return torch.zeros(n, 1, size, size, size, dtype=torch.uint8)
+    if kind in ("blobs", "speckle", "noise"):
+        return torch.zeros(n, 1, size, size, dtype=torch.uint8)
+    raise ValueError(f"unknown synthetic kind {kind}")
+
+
 def synthetic_images(kind: str, n: int, channels: int = 1, size: int = 32, seed: int = 0, mix: int = 10) -> torch.Tensor:
     """kind "speckle": blobs with ``mix`` percent of uniform noise blended in -- a near-distribution OOD set whose
-    AUROC against plain blobs is neither 0.5 nor saturated (used to make the AUROC checks sensitive)."""
+    AUROC against plain blobs is neither 0.5 nor saturated (used to make the AUROC checks sensitive).  kind "lesion": blobs
+    with one disc of uniform noise, ``mix`` percent of the extent across (``synthetic_masks`` has the disc)."""
+    if kind == "lesion":
+        return _lesion(n, channels, size, seed, mix)[0]
     gen = torch.Generator().manual_seed(seed)
     if kind == "blobs3d":
         return scale_intensity(_blobs3d(n, channels, size, gen))
@@ -197,6 +235,22 @@ def transform_image(a: torch.Tensor, image_roi=None, image_size=None, add_vflip=
     if image_size:
         a = F.interpolate(a[None], size=(int(image_size),) * (a.ndim - 1), mode="area")[0]
     a = scale_intensity(a[None])[0]
+    if add_vflip:
+        a = torch.flip(a, dims=(1,))
+    if add_hflip:
+        a = torch.flip(a, dims=(2,))
+    return a.contiguous()
+
+
+def transform_mask(m: torch.Tensor, image_roi=None, image_size=None, add_vflip=False, add_hflip=False) -> torch.Tensor:
+    """The geometry of ``transform_image`` for a ground-truth mask [1, *spatial] (anything != 0 is inside): centre crop, area
+    resize followed by >= 0.5 (at least half of the pixel was inside), the same flips; no intensity scaling.  -> uint8 0 / 1."""
+    a = (m != 0).to(torch.float32)
+    if image_roi:
+        a = center_crop(a, image_roi)
+    if image_size:
+        a = F.interpolate(a[None], size=(int(image_size),) * (a.ndim - 1), mode="area")[0]
+    a = (a >= 0.5).to(torch.uint8)
     if add_vflip:
         a = torch.flip(a, dims=(1,))
     if add_hflip:
@@ -385,16 +439,63 @@ def load_ids(ids: str, is_grayscale: bool = False, first_n=None, spatial_dimensi
     return imgs, row
 
 
+def load_masks(mask_ids: str, ids: str, names, shapes, first_n=None, spatial_dimension: int = 2, **transform):
+    """The masks of the images ``load_ids(ids, ...)`` returned (``names``, and ``shapes`` = their transformed shapes), as a list
+    of uint8 [1, *spatial] tensors.  ``mask_ids``: "auto" (``ids`` is a synthetic spec: ``synthetic_masks``), an ``.npz`` with
+    ``masks`` [N, *spatial] or [N, 1, *spatial] (and optionally ``names``, which must be the images'), or a one-row CSV of
+    files.  ``first_n`` truncates like the images'.  A count or an extent that differs from the images' is a ValueError."""
+    mask_ids, ids = str(mask_ids), str(ids)
+    if mask_ids == "auto":
+        if not ids.startswith("synthetic:"):
+            raise ValueError(f"masks 'auto' belong to a synthetic: spec, not to {ids}")
+        kind, kw = _parse_spec(ids)
+        raw = list(synthetic_masks(kind, kw["n"], kw["channels"], kw["size"], kw["seed"], kw["mix"]))
+    else:
+        p = Path(mask_ids)
+        if not p.exists():
+            raise FileNotFoundError(f"Cannot find mask file {p}")
+        if p.suffix == ".npz":
+            z = np.load(p, allow_pickle=False)
+            if "masks" not in z:
+                raise ValueError(f"{p}: a mask archive holds an array 'masks'")
+            m = torch.from_numpy(np.asarray(z["masks"]) != 0)
+            if m.ndim == spatial_dimension + 1:
+                m = m[:, None]
+            if m.ndim != spatial_dimension + 2 or m.shape[1] != 1:
+                raise ValueError(f"{p}: masks of shape {tuple(m.shape)} are not [N, *spatial{spatial_dimension}] or [N, 1, *spatial]")
+            if "names" in z:
+                theirs = [str(s) for s in z["names"]][: int(first_n)] if first_n else [str(s) for s in z["names"]]
+                if theirs != list(names):
+                    raise ValueError(f"{p}: the masks' names differ from the images' names")
+            raw = list(m)
+        else:
+            with open(p, "r") as f:
+                row = [s.strip() for s in f.readline().strip().split(",") if s.strip()]
+            if first_n:
+                row = row[: int(first_n)]
+            raw = [channel_first(read_image(path), path, True, spatial_dimension) for path in row]
+    if first_n:
+        raw = raw[: int(first_n)]
+    if len(raw) != len(names):
+        raise ValueError(f"{mask_ids}: {len(raw)} masks for {len(names)} images")
+    masks = [transform_mask(m, **transform) for m in raw]
+    for m, shape, name in zip(masks, shapes, names):
+        if tuple(m.shape[1:]) != tuple(shape[1:]):
+            raise ValueError(f"{mask_ids}: the mask of {name} is {tuple(m.shape[1:])} after the transforms, its image {tuple(shape[1:])}")
+    return masks
+
+
 class ListLoader:
     """Minimal stand-in for monai ThreadDataLoader over a cached, transformed dataset."""
 
     def __init__(self, images, names: List[str], batch_size: int, drop_last: bool = False,
-                 indices: List[int] = None, all_names: List[str] = None):
+                 indices: List[int] = None, all_names: List[str] = None, masks=None):
         # images: one [N, C, *spatial] tensor, or a list of [C, *spatial] tensors when the transformed shapes
         # differ (then a batch is stacked on demand and must be homogeneous, like torch's default collate)
         self.images, self.names, self.batch_size, self.drop_last = images, names, batch_size, drop_last
         self.indices = list(range(len(names))) if indices is None else list(indices)  # global image ids
         self.all_names = list(names) if all_names is None else list(all_names)
+        self.masks = masks  # None, or uint8 [N, 1, *spatial] / a list of [1, *spatial] parallel to ``images``: batches carry "mask"
 
     def __len__(self):
         n = len(self.names)
@@ -412,8 +513,12 @@ class ListLoader:
                     raise RuntimeError(f"cannot batch images of different shapes {[tuple(a.shape) for a in image]}: "
                                        "pass --image_roi / --image_size, or --batch_size=1")
                 image = torch.stack(image)
-            yield {"image": image, "image_meta_dict": {"filename_or_obj": self.names[s:e]},
-                   "index": self.indices[s:e]}
+            batch = {"image": image, "image_meta_dict": {"filename_or_obj": self.names[s:e]},
+                     "index": self.indices[s:e]}
+            if self.masks is not None:
+                mask = self.masks[s:e]
+                batch["mask"] = torch.stack(mask) if isinstance(mask, list) else mask
+            yield batch
 
 
 def partition(n_items: int, rank: int, world: int) -> List[int]:
@@ -423,7 +528,9 @@ def partition(n_items: int, rank: int, world: int) -> List[int]:
 
 def get_data_loader(ids: str, batch_size: int, first_n=None, is_grayscale: bool = False, image_size=None,
                     add_vflip: bool = False, add_hflip: bool = False, drop_last: bool = False,
-                    spatial_dimension: int = 2, image_roi=None, rank: int = 0, world: int = 1) -> ListLoader:
+                    spatial_dimension: int = 2, image_roi=None, rank: int = 0, world: int = 1, mask_ids=None) -> ListLoader:
+    """``mask_ids`` (None: batches are the plain ones): "auto", an ``.npz`` or a one-row CSV (``load_masks``); every batch then
+    carries "mask", uint8 [B, 1, *spatial] of 0 / 1, truncated and partitioned exactly like the images."""
     imgs, names = load_ids(ids, is_grayscale=is_grayscale, first_n=first_n, spatial_dimension=spatial_dimension,
                            image_roi=image_roi, image_size=image_size, add_vflip=add_vflip, add_hflip=add_hflip)
     for a, n in zip(imgs, names):
@@ -435,4 +542,11 @@ def get_data_loader(ids: str, batch_size: int, first_n=None, is_grayscale: bool 
     if len({tuple(a.shape) for a in mine}) <= 1:
         c = 1 if is_grayscale else 3
         mine = torch.stack(mine) if mine else torch.zeros((0, c) + (0,) * spatial_dimension)
-    return ListLoader(mine, [names[i] for i in idx], batch_size, drop_last, indices=idx, all_names=names)
+    my_masks = None
+    if mask_ids is not None:
+        masks = load_masks(mask_ids, ids, names, [tuple(a.shape) for a in imgs], first_n=first_n, spatial_dimension=spatial_dimension,
+                           image_roi=image_roi, image_size=image_size, add_vflip=add_vflip, add_hflip=add_hflip)
+        my_masks = [masks[i] for i in idx]
+        if torch.is_tensor(mine):
+            my_masks = torch.stack(my_masks) if my_masks else torch.zeros((0, 1) + (0,) * spatial_dimension, dtype=torch.uint8)
+    return ListLoader(mine, [names[i] for i in idx], batch_size, drop_last, indices=idx, all_names=names, masks=my_masks)

@@ -155,6 +155,53 @@ def main_zmaps(args, out_data=None):
     return dict(zip(out_data, scores))
 
 
+def score_pixels(out_npz, in_npz=None, key: str = "z_mse_map"):
+    """Pixel-level metrics of one out set (pixels_<name>.npz of ``reconstruct.py --pixel_metrics 1``) for the Z-map ``key``: a dict
+    of auroc, ap, best_dice, best_dice_threshold, nan_pixels and mean_dice {threshold: the mean per-image Dice}
+    (``pixel_metrics.summarize``).  ``in_npz`` given: the in set's pixels are pooled in as negatives of the histogram (the
+    per-image Dice stays the out set's).  A path or the loaded mapping each."""
+    from . import pixel_metrics as pm
+
+    if key not in pm.KEYS:
+        raise ValueError(f"score_pixels: key must be one of {pm.KEYS}, got {key!r}")
+    c = pm.KEYS.index(key)
+    z = np.load(out_npz) if isinstance(out_npz, (str, Path)) else out_npz
+    hist = np.asarray(z["hist"])
+    if hist.ndim != 3 or hist.shape[:2] != (2, 2) or hist.shape[2] != int(z["nbins"]) + 1:
+        raise ValueError(f"score_pixels: hist of {hist.shape} for nbins = {int(z['nbins'])} is no [2, 2, nbins + 1] table")
+    if in_npz is not None:
+        zi = np.load(in_npz) if isinstance(in_npz, (str, Path)) else in_npz
+        if (float(zi["lo"]), float(zi["hi"]), int(zi["nbins"])) != (float(z["lo"]), float(z["hi"]), int(z["nbins"])):
+            raise ValueError("score_pixels: the in set's histogram has another range or another number of bins")
+        hist = pm.pool_negatives(hist, np.asarray(zi["hist"]))
+    return pm.summarize(hist[c], float(z["lo"]), float(z["hi"]), np.asarray(z["counts"])[:, c], np.asarray(z["thresholds"]))
+
+
+def main_pixels(args, out_data=None):
+    """``ood_detection.py --score pixel``: per out set the pixel AUROC, AP, best Dice and the mean per-image Dice at the fixed
+    thresholds, from pixels_<name>.npz (and pixels_in.npz with --pixel_include_in 1)."""
+    model = args.model_name
+    run_dir = Path(args.output_dir) / model
+    print(f"Run directory: {str(run_dir)}")
+    out_dir = run_dir / "ood"
+    key = getattr(args, "zmap_key", "z_mse_map")
+    include_in = bool(getattr(args, "pixel_include_in", 0))
+    print(f"Pixel metrics of the Z-map {key}" + (", the in set's pixels pooled in as negatives" if include_in else ""))
+    if out_data is None:
+        out_data = out_datasets_for(model)
+    got = {}
+    for o in out_data:
+        s = got[o] = score_pixels(out_dir / f"pixels_{o}.npz", out_dir / "pixels_in.npz" if include_in else None, key)
+        print(f"Pixel AUC for {model} vs {o}: {s['auroc'] * 100:.2f}")
+        print(f"Pixel AP for {model} vs {o}: {s['ap'] * 100:.2f}")
+        print(f"Best Dice for {model} vs {o}: {s['best_dice']:.4f} at Z >= {s['best_dice_threshold']:.4f}")
+        for t, d in s["mean_dice"].items():
+            print(f"Mean image Dice for {model} vs {o} at Z > {t:g}: {d:.4f}")
+        if s["nan_pixels"]:
+            print(f"NaN pixels of {o} (not scored): {s['nan_pixels']}")
+    return got
+
+
 def main(args, out_data=None):
     model = args.model_name
     run_dir = Path(args.output_dir) / model

@@ -862,6 +862,84 @@ def map_blur(maps, sigma: float = None, taps=None, out=None):
     return out
 
 
+# ---- pixel-level metrics of the maps against ground-truth masks ------------------------------------
+
+MAP_HIST_MAX_BINS = 8191  # kHistMaxBins of csrc/pixel_metrics.hip: two classes of nbins + 1 counters in 64 KB of LDS
+MAP_COUNTS_MAX_K = 8      # kCountsMaxK
+MAP_HIST_MAX_PARTS = 256  # one workgroup per CU; a workgroup takes at least MAP_HIST_ELEMS_PER_PART elements
+MAP_HIST_ELEMS_PER_PART = 16384
+
+
+def map_hist_parts(elems: int) -> int:
+    """The default number of workgroups (= slabs) of ``map_mask_hist`` for ``elems`` map values."""
+    return max(1, min(MAP_HIST_MAX_PARTS, -(-int(elems) // MAP_HIST_ELEMS_PER_PART)))
+
+
+def _maps_and_masks(maps, masks, what):
+    """The two operands as they are, or ValueError: contiguous device tensors of one shape [N, ...], fp32 and uint8."""
+    for name, t, dtype in (("maps", maps, torch.float32), ("masks", masks, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor on a ROCm device (no CPU fallback)")
+    if maps.ndim < 2 or maps.shape != masks.shape or maps.device != masks.device or maps.numel() == 0:
+        raise ValueError(f"{what} wants maps and masks of one shape [N, ...] on one device, got {tuple(maps.shape)} and "
+                         f"{tuple(masks.shape)}")
+    return int(maps.shape[0]), int(maps.numel() // maps.shape[0])
+
+
+def map_mask_hist(maps, masks, lo: float, hi: float, nbins: int, total=None, parts: int = None):
+    """The two-class histogram of ``maps`` [N, ...] (fp32) against ``masks`` of the same shape (uint8, class 1 = mask != 0) over
+    ``nbins`` equal bins of [lo, hi): int64 [2, nbins + 1] on the device, values below / above the range in the first / last bin,
+    NaN in column ``nbins``.  ``total`` given: added into (it may overlap no input).  bin = (v - lo) * inv_step in fp32 with
+    inv_step = nbins / (hi - lo) formed in float64 and rounded once.  ``parts``: the number of workgroups, each with a slab of
+    its own (default ``map_hist_parts``); the counts do not depend on it."""
+    lib = _lib.load()
+    N, P = _maps_and_masks(maps, masks, "map_mask_hist")
+    nbins = int(nbins)
+    if not 1 <= nbins <= MAP_HIST_MAX_BINS:
+        raise ValueError(f"map_mask_hist: nbins must lie in 1 .. {MAP_HIST_MAX_BINS}, got {nbins}")
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo):
+        raise ValueError(f"map_mask_hist: the range must be finite with lo < hi, got [{lo}, {hi})")
+    inv_step = float(np.float32(nbins / (hi - lo)))
+    parts = map_hist_parts(N * P) if parts is None else int(parts)
+    if parts < 1:
+        raise ValueError(f"map_mask_hist: parts must be at least 1, got {parts}")
+    shape = (2, nbins + 1)
+    if total is None:
+        total, acc = torch.empty(shape, dtype=torch.int64, device=maps.device), 0
+    elif (not isinstance(total, torch.Tensor) or tuple(total.shape) != shape or total.dtype != torch.int64
+          or not total.is_contiguous() or total.device != maps.device):
+        raise ValueError(f"map_mask_hist: total must be a contiguous int64 {shape} tensor on {maps.device}")
+    else:
+        acc = 1
+    slabs = torch.empty((parts,) + shape, dtype=torch.int32, device=maps.device)  # (uint32 counters)
+    check(lib.ddpm_map_mask_hist_f32(ptr(maps), ptr(masks), N, P, float(np.float32(lo)), inv_step, nbins, parts, ptr(slabs),
+                                     ptr(total), acc, stream_ptr()), "map_mask_hist")
+    return total
+
+
+def map_mask_counts(maps, masks, thresholds):
+    """int32 [N, K, 3] on the device: per image and threshold the TP, FP and FN pixels of the prediction ``v > threshold`` against
+    ``mask != 0`` (a NaN pixel is predicted negative).  ``thresholds``: 1 .. 8 values, a sequence or an fp32 device tensor [K]."""
+    lib = _lib.load()
+    N, P = _maps_and_masks(maps, masks, "map_mask_counts")
+    if isinstance(thresholds, torch.Tensor):
+        thr = thresholds
+        if not thr.is_cuda or thr.dtype != torch.float32 or thr.ndim != 1 or not thr.is_contiguous() or thr.device != maps.device:
+            raise ValueError(f"map_mask_counts: thresholds must be a contiguous float32 [K] tensor on {maps.device}")
+    else:
+        host = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+        thr = torch.empty((len(host),), dtype=torch.float32, device=maps.device)
+        if len(host):
+            thr.copy_(torch.from_numpy(host))
+    K = int(thr.numel())
+    if not 1 <= K <= MAP_COUNTS_MAX_K:
+        raise ValueError(f"map_mask_counts: 1 .. {MAP_COUNTS_MAX_K} thresholds, got {K}")
+    counts = torch.empty((N, K, 3), dtype=torch.int32, device=maps.device)
+    check(lib.ddpm_map_mask_counts_f32(ptr(maps), ptr(masks), N, P, ptr(thr), K, ptr(counts), stream_ptr()), "map_mask_counts")
+    return counts
+
+
 # ---- LPIPS-AlexNet pieces (src/losses/perceptual_loss.py:105-186) -------------------------------------
 
 def lpips_conv(x, weight, bias, stride: int, pad: int, relu: bool = True, in_scale=None, in_shift=None):

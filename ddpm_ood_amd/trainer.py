@@ -32,7 +32,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import _lib, ops, zmaps
+from . import _lib, ops, pixel_metrics, zmaps
 from .data import get_data_loader
 from .perceptual import PerceptualLoss
 from .scheduler import DDPMScheduler, PNDMScheduler
@@ -341,9 +341,20 @@ class Reconstruct(BaseTrainer):
         self.z_std_floor = float(getattr(args, "anomaly_z_std_floor", 0.01))
         if self.anomaly_z_maps:
             zmaps.check_flags(args.spatial_dimension, args.vqvae_checkpoint, self.z_sigma, self.z_std_floor)
+        # --pixel_metrics 1 (extension): the in / out sets' Z-maps against ground-truth masks (--out_masks), as a
+        # two-class histogram and per-image TP / FP / FN counts (ood/pixels_<name>.npz).  Off without the attribute.
+        self.pixel_metrics = bool(getattr(args, "pixel_metrics", 0))
+        if self.pixel_metrics:
+            self.px_lo, self.px_hi, self.px_bins, self.px_thresholds, self.px_masks = pixel_metrics.check_flags(
+                self.anomaly_z_maps, args.out_ids if bool(args.run_out) else None, getattr(args, "out_masks", None),
+                getattr(args, "pixel_bins", pixel_metrics.DEFAULT_BINS), getattr(args, "pixel_range", None) or pixel_metrics.DEFAULT_RANGE,
+                getattr(args, "pixel_thresholds", None) or pixel_metrics.DEFAULT_THRESHOLDS)
         super().__init__(args)
         if not self.found_checkpoint:
             raise FileNotFoundError("Failed to find a saved model checkpoint.")
+        self.last_pixels = None  # the same for --pixel_metrics 1 (the in / out sets)
+        self._px = None  # the running tables of the pass under way: hist (device), rows (host, one entry per batch)
+        self._px_thr = self._px_no_mask = None  # the thresholds / an all-zero mask batch on the device
         self.last_maps = None  # the maps of the last get_scores call (rank 0, --anomaly_maps 1), what _write puts into the .npz
         self.last_zmaps = None  # the same for --anomaly_z_maps 1 (the in / out sets)
         self.last_map_stats = None  # (MapStats, t values) of the last validation pass, merged over the ranks
@@ -429,6 +440,8 @@ class Reconstruct(BaseTrainer):
         self.last_maps = self.last_zmaps = None
         # --anomaly_z_maps 1: the validation pass accumulates the per-pixel statistics, every other pass is normalised by them
         z_stats = zmaps.MapStats() if self.anomaly_z_maps and dataset_name == "val" else None
+        self.last_pixels = None
+        self._px = {"hist": None, "rows": []} if self.pixel_metrics and dataset_name != "val" else None
         z_skipped = 0
         t_values = [int(t) for t in reversed(self.make_scheduler().timesteps)[1::inference_skip_factor]
                     if (self.max_t_start is None or int(t) <= int(self.max_t_start))
@@ -490,7 +503,7 @@ class Reconstruct(BaseTrainer):
             if maps is not None:
                 maps_all.append(maps.cpu())  # one device->host copy per batch, after the batch's synchronisation
             if per_t_maps is not None:  # after the guard: the statistics see the per-t maps of the scores that are kept
-                z_skipped += self._z_batch(z_stats, scores, per_t_maps, t_values, zmaps_all)
+                z_skipped += self._z_batch(z_stats, scores, per_t_maps, t_values, zmaps_all, batch.get("mask"))
             ids_all.append(torch.tensor(batch["index"], dtype=torch.int32))
             names_all.extend(batch["image_meta_dict"]["filename_or_obj"])
             if quiet:
@@ -607,11 +620,13 @@ class Reconstruct(BaseTrainer):
         t2 = time.time()
         return scores, t_values, n_recon, n_fwd, B, t2 - t1, maps, per_t_maps
 
-    def _z_batch(self, z_stats, scores, per_t_maps, t_values, zmaps_all):
+    def _z_batch(self, z_stats, scores, per_t_maps, t_values, zmaps_all, mask=None):
         """--anomaly_z_maps 1, one batch after the numeric guard.  Validation pass (``z_stats`` given): the per-t maps of the
         images whose scores are all finite go into the running statistics (one launch); returns how many images were left out.
         Any other pass: the batch's Z-maps [B, 2, H, W] -- one launch, one more per batch when smoothing -- are appended to
-        ``zmaps_all`` on the host (one device->host copy per batch, after the batch's synchronisation)."""
+        ``zmaps_all`` on the host (one device->host copy per batch, after the batch's synchronisation).  --pixel_metrics 1: the
+        batch's Z-maps, still on the device, are also counted against ``mask`` (uint8 [B, 1, H, W]; None: all zero), per channel
+        one histogram launch into the pass's table and one counts launch; the counts ride to the host inside the same copy."""
         B, n_t = per_t_maps.shape[:2]
         if z_stats is not None:
             finite = torch.isfinite(scores).all(dim=2).all(dim=1)
@@ -630,8 +645,42 @@ class Reconstruct(BaseTrainer):
             if self._z_taps is None:
                 self._z_taps = torch.from_numpy(ops.gaussian_taps(self.z_sigma).astype(np.float32)).to(self.device)
             z = ops.map_blur(z.reshape(B * 2, H, W), taps=self._z_taps)
-        zmaps_all.append(z.reshape(B, 2, H, W).cpu())
+        if self._px is None:
+            zmaps_all.append(z.reshape(B, 2, H, W).cpu())
+            return 0
+        counts, mask_pixels = self._px_batch(z.reshape(B, 2, H * W), mask)
+        # one copy: each image's Z-maps travel as their int32 bit patterns with the int32 counts behind them (every bit is kept)
+        both = torch.cat([z.reshape(B, 2 * H * W).view(torch.int32), counts.reshape(B, -1)], dim=1).cpu()
+        zmaps_all.append(both[:, :2 * H * W].contiguous().view(torch.float32).reshape(B, 2, H, W))
+        rows = both[:, 2 * H * W:].contiguous()
+        self._px["rows"].append(torch.cat([rows, mask_pixels.to(torch.int32)[:, None]], dim=1))
         return 0
+
+    def _px_batch(self, z, mask):
+        """--pixel_metrics 1, one batch: ``z`` [B, 2, H W] on the device against ``mask``.  Returns (counts int32 [B, 2, K, 3] on
+        the device, the masks' pixel counts [B] on the host); the histograms are added into the pass's [2, 2, nbins + 1] table."""
+        B, _, P = z.shape
+        if P >= 1 << 31:
+            raise ValueError(f"--pixel_metrics 1: maps of {P} pixels do not fit the 32-bit counts")
+        if mask is None:  # (the in set, an out set without masks: every pixel is a negative)
+            if self._px_no_mask is None or self._px_no_mask.shape[0] < B or self._px_no_mask.shape[1] != P:
+                self._px_no_mask = torch.zeros((B, P), dtype=torch.uint8, device=self.device)
+            m, mask_pixels = self._px_no_mask[:B], torch.zeros(B, dtype=torch.int64)
+        else:
+            if mask.shape[0] != B or mask.numel() != B * P:
+                raise ValueError(f"--pixel_metrics 1: masks of {tuple(mask.shape)} for maps of {B} x {P} pixels")
+            mask_pixels = (mask.reshape(B, P) != 0).sum(dim=1).cpu()
+            m = mask.reshape(B, P).to(device=self.device, dtype=torch.uint8).contiguous()
+        if self._px["hist"] is None:
+            self._px["hist"] = torch.zeros((2, 2, self.px_bins + 1), dtype=torch.int64, device=self.device)
+        if self._px_thr is None:
+            self._px_thr = torch.tensor(self.px_thresholds, dtype=torch.float32, device=self.device)
+        counts = []
+        for c in range(2):
+            zc = z[:, c].contiguous()
+            ops.map_mask_hist(zc, m, self.px_lo, self.px_hi, self.px_bins, total=self._px["hist"][c])
+            counts.append(ops.map_mask_counts(zc, m, self._px_thr))
+        return torch.stack(counts, dim=1), mask_pixels
 
     def _z_set_tables(self, stats, t_values):
         mean, inv_std = stats.finalize(self.z_std_floor)
@@ -717,7 +766,35 @@ class Reconstruct(BaseTrainer):
                 self.last_zmaps = {"filename": np.asarray(stems), "t": np.asarray(t_values, dtype=np.int64),
                                    "z_lpips_map": np.ascontiguousarray(z[:, 0]), "z_mse_map": np.ascontiguousarray(z[:, 1]),
                                    "sigma": np.float64(self.z_sigma), "rel_floor": np.float64(self.z_std_floor)}
+            if self._px is not None:
+                self._collect_pixels(loader, results, t_values, local_ids, ids.cpu().tolist(), name_of, zmaps_all)
+        self._px = None
         return results
+
+    def _collect_pixels(self, loader, results, t_values, local_ids, gathered_ids, name_of, zmaps_all):
+        """--pixel_metrics 1: the histogram summed over the ranks (ONE all_reduce of the int64 table) and every rank's count rows
+        in the CSV's order of first appearance (the collective of the maps; its payload is fp32, so a count must stay below
+        2^24).  Rank 0 keeps both in ``last_pixels`` for ``_write``."""
+        hist = self._px["hist"]
+        K = len(self.px_thresholds)
+        pixels = int(zmaps_all[0].shape[2] * zmaps_all[0].shape[3])
+        if self.ddp:
+            if pixels >= 1 << 24:
+                raise ValueError(f"--pixel_metrics 1: a count of up to {pixels} pixels is not exact in the fp32 payload of the "
+                                 f"gather (H W must stay below 2^24 with more than one rank)")
+            if dist.get_backend() == "gloo" and hist.is_cuda:  # (the test hook of gather_scores)
+                hist = hist.cpu()
+            dist.all_reduce(hist, op=dist.ReduceOp.SUM)
+        got = self._gather_map_rows("--pixel_metrics 1", loader, results, local_ids, gathered_ids, name_of, self._px["rows"])
+        if got is not None:
+            stems, rows = got
+            rows = np.rint(rows).astype(np.int64)
+            self.last_pixels = {"filename": np.asarray(stems), "t": np.asarray(t_values, dtype=np.int64),
+                                "channels": np.asarray(zmaps.CHANNELS), "lo": np.float64(self.px_lo), "hi": np.float64(self.px_hi),
+                                "nbins": np.int64(self.px_bins), "hist": hist.cpu().numpy().astype(np.int64),
+                                "thresholds": np.asarray(self.px_thresholds, dtype=np.float32),
+                                "counts": rows[:, :-1].reshape(-1, 2, K, 3).astype(np.int32), "mask_pixels": rows[:, -1],
+                                "sigma": np.float64(self.z_sigma)}
 
     def _collect_maps(self, loader, results, t_values, local_ids, gathered_ids, name_of, maps_all):
         """The maps of every rank's images in the CSV's order of first appearance (rank 0 keeps them: ``last_maps``)."""
@@ -759,7 +836,11 @@ class Reconstruct(BaseTrainer):
             if self.anomaly_z_maps and self.last_zmaps is not None:
                 # filename [N], t [n_t], z_lpips_map / z_mse_map fp32 [N, H, W], sigma, rel_floor
                 np.savez(self.out_dir / f"zmaps_{name}.npz", **self.last_zmaps)
-        self.last_maps = self.last_zmaps = None
+            if self.pixel_metrics and self.last_pixels is not None:
+                # filename [N], t, channels, lo, hi, nbins, hist int64 [2, 2, nbins + 1], thresholds [K], counts int32 [N, 2, K, 3],
+                # mask_pixels [N], sigma
+                np.savez(self.out_dir / f"pixels_{name}.npz", **self.last_pixels)
+        self.last_maps = self.last_zmaps = self.last_pixels = None
 
     def reconstruct(self, args):
         if bool(args.run_val):
@@ -767,8 +848,9 @@ class Reconstruct(BaseTrainer):
         if bool(args.run_in):
             self._write(self.get_scores(self.in_loader, "in", args.inference_skip_factor), "in")
         if bool(args.run_out):
-            for out in args.out_ids.split(","):
+            for k, out in enumerate(args.out_ids.split(",")):
                 print(out)
+                masks = {"mask_ids": self.px_masks[k]} if self.pixel_metrics and self.px_masks[k] else {}
                 flips = {}
                 if "vflip" in out:
                     out = out.replace("_vflip", "")
@@ -779,7 +861,7 @@ class Reconstruct(BaseTrainer):
                 else:
                     suffix = ""
                 out_loader = get_data_loader(out, first_n=int(args.first_n) if args.first_n else args.first_n,
-                                             **flips, **self._loader_args)
+                                             **flips, **masks, **self._loader_args)
                 dataset_name = dataset_stem(out) + suffix
                 self._write(self.get_scores(out_loader, "out", args.inference_skip_factor), dataset_name)
 

@@ -480,6 +480,26 @@ int ddpm_map_zscore_f32(const float *values, const float *mean, const float *inv
 int ddpm_map_blur_f32(const float *in, float *out, const float *taps, int radius, int N, int H, int W, ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Pixel-level evaluation of maps against ground-truth masks (--pixel_metrics 1).  Entry points added without
+ * an ABI bump; no size function (the caller chooses `parts` and allocates the slabs); every pointer but the stream is a device
+ * buffer.  Integer results: independent of the order of the additions, no global atomics, no buffer's previous contents read
+ * (but `total` with accumulate != 0).
+ * ---------------------------------------------------------------------------------- */
+/* Two-class histogram of maps [N, P] (fp32) against masks [N, P] (uint8; class 1 = mask != 0).  Bin of a value v, in fp32 with
+ * every operation rounded once:  b = (v - lo) * inv_step;  NaN -> column nbins;  b < 0 -> 0;  b >= nbins (+inf included) ->
+ * nbins - 1;  else (int)b.  `parts` workgroups each store a private histogram into slabs [parts, 2, nbins + 1] (uint32), then
+ * total [2, nbins + 1] (int64) = (accumulate ? total : 0) + the sum of the slabs in ascending order.  16-byte map loads from
+ * the first 16-byte boundary of maps on; any alignment of masks.  Refused: nbins outside 1 .. 8191, N * P >= 2^32, parts
+ * outside 1 .. 65536, lo not finite or inv_step not positive and finite, slabs / total overlapping another operand.        */
+int ddpm_map_mask_hist_f32(const float *maps, const uint8_t *masks, int N, int64_t P, float lo, float inv_step, int nbins,
+                           int parts, uint32_t *slabs, int64_t *total, int accumulate, ddpm_stream_t stream);
+/* counts [N, K, 3] (int32) = per image and threshold the pixels with (v > thr and mask), (v > thr and not mask), (not v > thr
+ * and mask): TP, FP, FN; a NaN pixel is predicted negative.  thresholds: [K] fp32 on the device, 1 <= K <= 8; P < 2^31.  One
+ * workgroup per image: a row's counts depend neither on N nor on its place in the batch.  counts may overlap no input.       */
+int ddpm_map_mask_counts_f32(const float *maps, const uint8_t *masks, int N, int64_t P, const float *thresholds, int K,
+                             int32_t *counts, ddpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Loss terms of VQ-VAE training (src/trainers/vqvae_trainer.py: 0.001 x PerceptualLoss + JukeboxLoss in the generator loss;
  * SURVEY.md A.8).  Entry points added without an ABI bump.  Everything is deterministic (fixed-order sums, no atomics).
  * ---------------------------------------------------------------------------------- */

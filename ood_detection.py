@@ -17,10 +17,15 @@ def parse_args(argv=None):
                    help="extension: which Z-score feeds the AUROC (the reference hard-codes mse)")
     p.add_argument("--out_data", default=None,
                    help="extension: comma list of OOD set names (default: picked from --model_name)")
-    p.add_argument("--score", default="reconstruction", choices=["reconstruction", "likelihood", "zmap"],
+    p.add_argument("--score", default="reconstruction", choices=["reconstruction", "likelihood", "zmap", "pixel"],
                    help="extension: likelihood reads the likelihood_*.csv files of likelihood.py and ranks by NLL; zmap reads the "
-                        "zmaps_*.npz files of reconstruct.py --anomaly_z_maps 1 and ranks by a reduction of the per-pixel Z-map")
-    p.add_argument("--zmap_key", default="z_mse_map", choices=["z_mse_map", "z_lpips_map"], help="--score zmap: which Z-map")
+                        "zmaps_*.npz files of reconstruct.py --anomaly_z_maps 1 and ranks by a reduction of the per-pixel Z-map; "
+                        "pixel reads the pixels_*.npz files of reconstruct.py --pixel_metrics 1 and prints the pixel-level AUROC, "
+                        "AP and Dice of the Z-map against the ground-truth masks")
+    p.add_argument("--zmap_key", default="z_mse_map", choices=["z_mse_map", "z_lpips_map"],
+                   help="--score zmap / pixel: which Z-map")
+    p.add_argument("--pixel_include_in", type=int, default=0,
+                   help="--score pixel: 1 pools the in set's pixels (pixels_in.npz) into the negatives")
     p.add_argument("--zmap_reduce", default="mean", choices=["mean", "max"], help="--score zmap: mean or maximum over the pixels")
     return p.parse_args(argv)
 
@@ -32,5 +37,5 @@ if __name__ == "__main__":
 
     for model in args.model_name.split(","):
         args.model_name = model
-        run = {"likelihood": ood.main_likelihood, "zmap": ood.main_zmaps}.get(args.score, ood.main)
+        run = {"likelihood": ood.main_likelihood, "zmap": ood.main_zmaps, "pixel": ood.main_pixels}.get(args.score, ood.main)
         run(args, out_data=args.out_data.split(",") if args.out_data else None)

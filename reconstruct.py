@@ -66,6 +66,12 @@ _EXTENSIONS = [
                                "averaged over the t-starts (2-D pixel-space models)"),
     ("anomaly_z_sigma", float, 0.0, "Gaussian smoothing of the Z-maps in pixels (0: none; below 4.125)"),
     ("anomaly_z_std_floor", float, 0.01, "a pixel's std is floored at this fraction of the largest std of its (t, channel)"),
+    ("pixel_metrics", int, 0, "1 (with --anomaly_z_maps 1): also write ood/pixels_<name>.npz, the in / out sets' Z-maps against "
+                              "ground-truth masks: a two-class histogram and per-image TP / FP / FN counts (ood_detection.py --score pixel)"),
+    ("out_masks", str, None, "--pixel_metrics 1: comma list parallel to --out_ids; an entry is auto (a synthetic: spec), an .npz "
+                             "with 'masks', a one-row CSV of mask files, or empty for a set without masks (all zero)"),
+    ("pixel_bins", int, 4096, "--pixel_metrics 1: bins of the histogram (1 .. 8191)"),
+    ("pixel_thresholds", str, "2,3,4", "--pixel_metrics 1: comma list of 1 .. 8 fixed Z thresholds of the per-image Dice"),
 ]
 
 
@@ -82,6 +88,8 @@ def build_parser():
         if typ is not None:
             kw["type"] = typ
         ext.add_argument(f"--{name}", **kw)
+    ext.add_argument("--pixel_range", type=float, nargs=2, default=[-16.0, 48.0], metavar=("LO", "HI"),
+                     help="--pixel_metrics 1: the Z range the bins divide; values outside fall into the first / last bin")
     ext.add_argument("--timestep_list", default="monai", choices=["monai", "diffusers"],
                      help="100-entry or 101-entry PLMS timestep list (Q9)")
     return parser
