@@ -12,29 +12,12 @@
 // Bytes: 5 N P in, parts 2 (nbins + 1) 4 out and in again, 2 (nbins + 1) 8 out.
 // map_mask_counts: one workgroup of 256 threads per image, per-thread integer counters for the K <= 8 thresholds, a butterfly
 // over the wave (__shfl_xor 32 .. 1), the four waves' partials through LDS, 3 K plain stores.
-#include "common.h"
+#include "pixel_common.h"
 
 namespace ddpm {
 
-static bool pm_overlap(const void *p, double p_bytes, const void *q, double q_bytes) {
-  const double a0 = (double)(uintptr_t)p, b0 = (double)(uintptr_t)q;
-  return a0 < b0 + q_bytes && b0 < a0 + p_bytes;
-}
-
-constexpr int kHistMaxBins = 8191;              // 2 classes x (8191 + 1) counters x 4 B = 64 KB
 constexpr int kHistCounters = 2 * (kHistMaxBins + 1);
 constexpr int kPmBlock = 256;
-constexpr int kCountsMaxK = 8;
-
-// b = (v - lo) * inv_step in fp32, each operation rounded once; the comparisons come before the conversion, so that no value
-// outside the int range is ever converted
-__device__ __forceinline__ int pm_bin(float v, float lo, float inv_step, int nbins) {
-  const float b = (v - lo) * inv_step;
-  if (b != b) return nbins;
-  if (b < 0.0f) return 0;
-  if (b >= (float)nbins) return nbins - 1;
-  return (int)b;
-}
 
 __global__ __launch_bounds__(kPmBlock) void map_mask_hist_kernel(const float *__restrict__ maps, const uint8_t *__restrict__ masks,
                                                                  uint32_t total_elems, uint32_t head, uint32_t chunks,

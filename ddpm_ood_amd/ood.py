@@ -155,11 +155,13 @@ def main_zmaps(args, out_data=None):
     return dict(zip(out_data, scores))
 
 
-def score_pixels(out_npz, in_npz=None, key: str = "z_mse_map"):
+def score_pixels(out_npz, in_npz=None, key: str = "z_mse_map", regions_npz=None, pro_fpr: float = 0.3):
     """Pixel-level metrics of one out set (pixels_<name>.npz of ``reconstruct.py --pixel_metrics 1``) for the Z-map ``key``: a dict
     of auroc, ap, best_dice, best_dice_threshold, nan_pixels and mean_dice {threshold: the mean per-image Dice}
     (``pixel_metrics.summarize``).  ``in_npz`` given: the in set's pixels are pooled in as negatives of the histogram (the
-    per-image Dice stays the out set's).  A path or the loaded mapping each."""
+    per-image Dice stays the out set's).  ``regions_npz`` given (regions_<name>.npz of ``--pixel_regions 1``): also aupro (the
+    region-overlap curve up to the false-positive rate ``pro_fpr``; the in set's pixels, when pooled, enter that rate only) and
+    region_recall, component_precision, component_f1 {threshold: value}.  A path or the loaded mapping each."""
     from . import pixel_metrics as pm
 
     if key not in pm.KEYS:
@@ -174,7 +176,19 @@ def score_pixels(out_npz, in_npz=None, key: str = "z_mse_map"):
         if (float(zi["lo"]), float(zi["hi"]), int(zi["nbins"])) != (float(z["lo"]), float(z["hi"]), int(z["nbins"])):
             raise ValueError("score_pixels: the in set's histogram has another range or another number of bins")
         hist = pm.pool_negatives(hist, np.asarray(zi["hist"]))
-    return pm.summarize(hist[c], float(z["lo"]), float(z["hi"]), np.asarray(z["counts"])[:, c], np.asarray(z["thresholds"]))
+    out = pm.summarize(hist[c], float(z["lo"]), float(z["hi"]), np.asarray(z["counts"])[:, c], np.asarray(z["thresholds"]))
+    if regions_npz is not None:
+        zr = np.load(regions_npz) if isinstance(regions_npz, (str, Path)) else regions_npz
+        if (float(zr["lo"]), float(zr["hi"]), int(zr["nbins"])) != (float(z["lo"]), float(z["hi"]), int(z["nbins"])) \
+                or np.asarray(zr["overlap"]).shape != hist.shape[1:]:
+            raise ValueError("score_pixels: the regions file has another range or another number of bins than the pixels file")
+        r = pm.summarize_regions(np.asarray(zr["overlap"])[c], np.asarray(zr["regions"]), hist[c], np.asarray(zr["components"])[:, c],
+                                 pro_fpr)
+        thr = [float(t) for t in np.asarray(zr["thresholds"])]
+        out["aupro"] = r["aupro"]
+        for name in ("region_recall", "component_precision", "component_f1"):
+            out[name] = dict(zip(thr, r[name]))
+    return out
 
 
 def main_pixels(args, out_data=None):
@@ -186,12 +200,14 @@ def main_pixels(args, out_data=None):
     out_dir = run_dir / "ood"
     key = getattr(args, "zmap_key", "z_mse_map")
     include_in = bool(getattr(args, "pixel_include_in", 0))
+    regions, pro_fpr = bool(getattr(args, "pixel_regions", 0)), float(getattr(args, "pixel_pro_fpr", 0.3))
     print(f"Pixel metrics of the Z-map {key}" + (", the in set's pixels pooled in as negatives" if include_in else ""))
     if out_data is None:
         out_data = out_datasets_for(model)
     got = {}
     for o in out_data:
-        s = got[o] = score_pixels(out_dir / f"pixels_{o}.npz", out_dir / "pixels_in.npz" if include_in else None, key)
+        s = got[o] = score_pixels(out_dir / f"pixels_{o}.npz", out_dir / "pixels_in.npz" if include_in else None, key,
+                                  out_dir / f"regions_{o}.npz" if regions else None, pro_fpr)
         print(f"Pixel AUC for {model} vs {o}: {s['auroc'] * 100:.2f}")
         print(f"Pixel AP for {model} vs {o}: {s['ap'] * 100:.2f}")
         print(f"Best Dice for {model} vs {o}: {s['best_dice']:.4f} at Z >= {s['best_dice_threshold']:.4f}")
@@ -199,6 +215,11 @@ def main_pixels(args, out_data=None):
             print(f"Mean image Dice for {model} vs {o} at Z > {t:g}: {d:.4f}")
         if s["nan_pixels"]:
             print(f"NaN pixels of {o} (not scored): {s['nan_pixels']}")
+        if regions:
+            print(f"AUPRO (FPR <= {pro_fpr:g}) for {model} vs {o}: {s['aupro'] * 100:.2f}")
+            for t in s["region_recall"]:
+                print(f"Regions for {model} vs {o} at Z > {t:g}: recall {s['region_recall'][t]:.4f}, component precision "
+                      f"{s['component_precision'][t]:.4f}, F1 {s['component_f1'][t]:.4f}")
     return got
 
 

@@ -940,6 +940,126 @@ def map_mask_counts(maps, masks, thresholds):
     return counts
 
 
+# ---- region-level metrics of the maps: connected components, region overlap, component counts -------
+
+MAP_LABEL_MAX_PIXELS = 16384  # kRgMaxPixels of csrc/regions.hip: a plane's 16-bit labels in 32 KB of LDS (128 x 128)
+
+
+def _planes(t, dtype, name, what):
+    """``t`` as it is, or ValueError: a contiguous [N, H, W] device tensor of ``dtype`` whose plane the labelling can hold."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor on a ROCm device (no CPU fallback)")
+    if t.ndim != 3 or t.numel() == 0:
+        raise ValueError(f"{what} wants {name} of shape [N, H, W], got {tuple(t.shape)}")
+    if t.shape[1] * t.shape[2] > MAP_LABEL_MAX_PIXELS:
+        raise ValueError(f"{what}: a plane of {t.shape[1]} x {t.shape[2]} pixels is above the maximum of {MAP_LABEL_MAX_PIXELS} "
+                         f"(128 x 128)")
+    return tuple(int(v) for v in t.shape)
+
+
+def _connectivity(connectivity, what):
+    if connectivity not in (4, 8):
+        raise ValueError(f"{what}: connectivity must be 4 or 8, got {connectivity!r}")
+    return int(connectivity)
+
+
+def _labels_and_regions(labels, regions, shape, device, what):
+    for name, t, want in (("labels", labels, tuple(shape)), ("regions", regions, (shape[0],))):
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous()
+                or tuple(t.shape) != want or t.device != device):
+            raise ValueError(f"{what}: {name} must be a contiguous int32 {want} tensor on {device}")
+
+
+def map_label(x, connectivity: int = 8, threshold: float = None):
+    """Connected components of [N, H, W] planes: of ``x != 0`` for a uint8 ``x`` (``threshold`` None), of ``x > threshold`` for an
+    fp32 ``x`` (a NaN pixel is outside).  Returns (labels int32 [N, H, W], regions int32 [N]) on the device: 0 outside, the
+    components 1 .. regions[n] in ascending order of their smallest flat pixel index, as ``scipy.ndimage.label`` numbers them
+    with the cross (``connectivity`` 4) or the 3 x 3 structure (8).  H W <= 16 384."""
+    lib = _lib.load()
+    what = "map_label"
+    connectivity = _connectivity(connectivity, what)
+    if threshold is None:
+        N, H, W = _planes(x, torch.uint8, "x (no threshold: a mask)", what)
+    else:
+        N, H, W = _planes(x, torch.float32, "x (with a threshold: a map)", what)
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=x.device)
+    regions = torch.empty((N,), dtype=torch.int32, device=x.device)
+    if threshold is None:
+        rc = lib.ddpm_map_label_u8(ptr(x), N, H, W, connectivity, ptr(labels), ptr(regions), stream_ptr())
+    else:
+        rc = lib.ddpm_map_label_f32(ptr(x), float(np.float32(threshold)), N, H, W, connectivity, ptr(labels), ptr(regions),
+                                    stream_ptr())
+    check(rc, what)
+    return labels, regions
+
+
+def map_region_overlap(maps, labels, regions, lo: float, hi: float, nbins: int, total=None):
+    """The per-region overlap table of ``maps`` (fp32 [N, ...]) against the regions of ``map_label`` (``labels`` of the maps'
+    shape, ``regions`` [N]) over the bins of ``map_mask_hist``: float64 [nbins + 1] on the device,
+    sum_n sum_r (region r's pixels in the bin) / (region r's pixels), NaN pixels in column ``nbins``.  ``total`` given: added
+    into, image by image, so that batches accumulated one after the other give the bits of one batch."""
+    lib = _lib.load()
+    what = "map_region_overlap"
+    if not isinstance(maps, torch.Tensor) or not maps.is_cuda or maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise ValueError(f"{what}: maps must be a contiguous {torch.float32} tensor on a ROCm device (no CPU fallback)")
+    if maps.ndim < 2 or maps.numel() == 0:
+        raise ValueError(f"{what} wants maps of shape [N, ...], got {tuple(maps.shape)}")
+    N, P = int(maps.shape[0]), int(maps.numel() // maps.shape[0])
+    if P > MAP_LABEL_MAX_PIXELS:
+        raise ValueError(f"{what}: a plane of {P} pixels is above the maximum of {MAP_LABEL_MAX_PIXELS} (128 x 128)")
+    _labels_and_regions(labels, regions, maps.shape, maps.device, what)
+    nbins = int(nbins)
+    if not 1 <= nbins <= MAP_HIST_MAX_BINS:
+        raise ValueError(f"{what}: nbins must lie in 1 .. {MAP_HIST_MAX_BINS}, got {nbins}")
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo):
+        raise ValueError(f"{what}: the range must be finite with lo < hi, got [{lo}, {hi})")
+    inv_step = float(np.float32(nbins / (hi - lo)))
+    shape = (nbins + 1,)
+    if total is None:
+        total, acc = torch.empty(shape, dtype=torch.float64, device=maps.device), 0
+    elif (not isinstance(total, torch.Tensor) or tuple(total.shape) != shape or total.dtype != torch.float64
+          or not total.is_contiguous() or total.device != maps.device):
+        raise ValueError(f"{what}: total must be a contiguous float64 {shape} tensor on {maps.device}")
+    else:
+        acc = 1
+    scratch = torch.empty((N,) + shape, dtype=torch.float64, device=maps.device)
+    check(lib.ddpm_map_region_overlap_f32(ptr(maps), ptr(labels), ptr(regions), N, P, float(np.float32(lo)), inv_step, nbins,
+                                          ptr(scratch), ptr(total), acc, stream_ptr()), what)
+    return total
+
+
+def map_component_counts(maps, masks, labels, regions, thresholds, connectivity: int = 8):
+    """int32 [N, K, 3] on the device: per image and threshold ``hit`` (the regions of ``labels`` / ``regions`` with a pixel
+    ``v > threshold``), ``pred`` (the connected components of ``v > threshold``) and ``false_pred`` (those components without a
+    pixel of ``mask != 0``).  ``maps`` fp32 and ``masks`` uint8 [N, H, W]; ``thresholds``: 1 .. 8 values, a sequence or an fp32
+    device tensor [K]."""
+    lib = _lib.load()
+    what = "map_component_counts"
+    connectivity = _connectivity(connectivity, what)
+    N, H, W = _planes(maps, torch.float32, "maps", what)
+    if _planes(masks, torch.uint8, "masks", what) != (N, H, W) or masks.device != maps.device:
+        raise ValueError(f"{what} wants maps and masks of one shape [N, H, W] on one device, got {tuple(maps.shape)} and "
+                         f"{tuple(masks.shape)}")
+    _labels_and_regions(labels, regions, maps.shape, maps.device, what)
+    if isinstance(thresholds, torch.Tensor):
+        thr = thresholds
+        if not thr.is_cuda or thr.dtype != torch.float32 or thr.ndim != 1 or not thr.is_contiguous() or thr.device != maps.device:
+            raise ValueError(f"{what}: thresholds must be a contiguous float32 [K] tensor on {maps.device}")
+    else:
+        host = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+        thr = torch.empty((len(host),), dtype=torch.float32, device=maps.device)
+        if len(host):
+            thr.copy_(torch.from_numpy(host))
+    K = int(thr.numel())
+    if not 1 <= K <= MAP_COUNTS_MAX_K:
+        raise ValueError(f"{what}: 1 .. {MAP_COUNTS_MAX_K} thresholds, got {K}")
+    counts = torch.empty((N, K, 3), dtype=torch.int32, device=maps.device)
+    check(lib.ddpm_map_component_counts_f32(ptr(maps), ptr(masks), ptr(labels), ptr(regions), N, H, W, ptr(thr), K, connectivity,
+                                            ptr(counts), stream_ptr()), what)
+    return counts
+
+
 # ---- LPIPS-AlexNet pieces (src/losses/perceptual_loss.py:105-186) -------------------------------------
 
 def lpips_conv(x, weight, bias, stride: int, pad: int, relu: bool = True, in_scale=None, in_shift=None):

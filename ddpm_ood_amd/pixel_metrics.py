@@ -144,6 +144,99 @@ def check_flags(anomaly_z_maps, out_ids, out_masks=None, bins=DEFAULT_BINS, valu
     return lo, hi, nbins, thr, masks
 
 
+# ---- region-level metrics (``--pixel_regions 1``) ----------------------------------------------------
+# The device side (``ops.map_label`` / ``map_region_overlap`` / ``map_component_counts``) leaves the number of ground-truth
+# regions per image, the overlap table float64 [nbins + 1] = sum over the regions of (the region's pixels in the bin) / (its
+# pixels) with the NaN pixels in the last column, and per image and threshold (hit, pred, false_pred).
+
+REGION_FLAG = "--pixel_regions 1"
+DEFAULT_CONNECTIVITY, DEFAULT_PRO_FPR = 8, 0.3
+MAX_REGION_PIXELS = 16384  # (ops.MAP_LABEL_MAX_PIXELS)
+
+
+def pro_curve(overlap, regions_total, hist):
+    """(fpr, pro), float64 [nbins + 1], entry j for k = nbins - j (from (0, 0) at k = nbins: nothing predicted) with "predicted at
+    k" = bin >= k:
+    PRO_k = (1 / R) sum_{k <= b < nbins} overlap[b], the mean over the R regions of the fraction of a region predicted, and
+    FPR_k = fp_k / negatives from row 0 of the [2, nbins + 1] histogram.  R == 0: ValueError; no negative pixel: fpr is NaN."""
+    w = np.asarray(overlap, dtype=np.float64)
+    h = _scored(hist)
+    if w.ndim != 1 or w.shape[0] != h.shape[1] + 1:
+        raise ValueError(f"an overlap table is [nbins + 1] beside a histogram [2, nbins + 1], got {w.shape} and {np.asarray(hist).shape}")
+    R = int(regions_total)
+    if R <= 0:
+        raise ValueError("region metrics: no ground-truth region")
+    pro = np.concatenate([[0.0], np.cumsum(w[:-1][::-1])]) / R  # entry j: k = nbins - j
+    neg = h[0].sum()
+    fp = np.concatenate([[0.0], np.cumsum(h[0][::-1])])
+    fpr = fp / neg if neg > 0 else np.full_like(fp, np.nan)
+    return fpr, pro
+
+
+def aupro(overlap, regions_total, hist, fpr_limit: float = DEFAULT_PRO_FPR) -> float:
+    """The trapezoid of PRO over FPR on [0, fpr_limit], the segment that crosses the limit cut there by linear interpolation,
+    divided by fpr_limit: 1 for a perfect map.  NaN without a negative pixel."""
+    fpr_limit = float(fpr_limit)
+    if not 0.0 < fpr_limit <= 1.0:
+        raise ValueError(f"aupro: fpr_limit must lie in (0, 1], got {fpr_limit}")
+    fpr, pro = pro_curve(overlap, regions_total, hist)
+    if np.isnan(fpr).any():
+        return float("nan")
+    area = 0.0
+    for j in range(1, len(fpr)):
+        x0, x1, y0, y1 = fpr[j - 1], fpr[j], pro[j - 1], pro[j]
+        if x1 <= fpr_limit:
+            area += (x1 - x0) * (y0 + y1) * 0.5
+        else:
+            if x0 < fpr_limit:
+                y_cut = y0 + (y1 - y0) * (fpr_limit - x0) / (x1 - x0)
+                area += (fpr_limit - x0) * (y0 + y_cut) * 0.5
+            break
+    return float(area / fpr_limit)
+
+
+def component_scores(components, regions):
+    """From integer ``components`` [N, K, 3] = (hit, pred, false_pred) and ``regions`` [N]: dict of float64 [K] arrays --
+    ``region_recall`` = sum hit / sum regions (NaN without a region), ``component_precision`` = 1 - sum false_pred / sum pred
+    (1 when nothing is predicted), ``component_f1`` of the two (0 when both are 0) and ``false_per_image`` = sum false_pred / N."""
+    c = np.asarray(components, dtype=np.float64)
+    r = np.asarray(regions, dtype=np.float64).reshape(-1)
+    if c.ndim != 3 or c.shape[2] != 3 or c.shape[0] != r.shape[0] or c.shape[0] == 0:
+        raise ValueError(f"components are [N, K, 3] (hit, pred, false_pred) beside regions [N], got {c.shape} and {r.shape}")
+    hit, pred, false_pred = c[..., 0].sum(axis=0), c[..., 1].sum(axis=0), c[..., 2].sum(axis=0)
+    total = r.sum()
+    recall = hit / total if total > 0 else np.full_like(hit, np.nan)
+    precision = np.where(pred > 0, 1.0 - false_pred / np.where(pred > 0, pred, 1.0), 1.0)
+    den = recall + precision
+    f1 = np.where(den > 0, 2.0 * recall * precision / np.where(den > 0, den, 1.0), 0.0)
+    return {"region_recall": recall, "component_precision": precision, "component_f1": f1, "false_per_image": false_pred / c.shape[0]}
+
+
+def check_region_flags(pixel_metrics, connectivity=DEFAULT_CONNECTIVITY, pro_fpr=DEFAULT_PRO_FPR):
+    """What ``Reconstruct`` refuses at construction when ``--pixel_regions 1`` is given (no device needed).  Returns
+    (connectivity, pro_fpr)."""
+    if not pixel_metrics:
+        raise ValueError(f"{REGION_FLAG} adds to the pixel metrics: it needs {FLAG}")
+    try:
+        conn = int(connectivity)
+        fpr = float(pro_fpr)
+    except (TypeError, ValueError):
+        raise ValueError(f"{REGION_FLAG}: --pixel_connectivity is 4 or 8 and --pixel_pro_fpr a number, got {connectivity!r} and "
+                         f"{pro_fpr!r}") from None
+    if conn != float(connectivity) or conn not in (4, 8):
+        raise ValueError(f"{REGION_FLAG}: --pixel_connectivity must be 4 or 8, got {connectivity}")
+    if not 0.0 < fpr <= 1.0:
+        raise ValueError(f"{REGION_FLAG}: --pixel_pro_fpr must lie in (0, 1], got {pro_fpr}")
+    return conn, fpr
+
+
+def summarize_regions(overlap, regions, hist, components, fpr_limit: float = DEFAULT_PRO_FPR):
+    """The numbers ``ood.score_pixels`` adds for one channel: aupro and ``component_scores`` as lists per threshold."""
+    out = {"aupro": aupro(overlap, int(np.asarray(regions).sum()), hist, fpr_limit)}
+    out.update({k: v.tolist() for k, v in component_scores(components, regions).items()})
+    return out
+
+
 def summarize(hist, lo: float, hi: float, counts=None, thresholds=None):
     """The numbers ``ood.score_pixels`` prints for one [2, nbins + 1] histogram (and the per-image counts [N, K, 3])."""
     nbins = np.asarray(hist).shape[1] - 1

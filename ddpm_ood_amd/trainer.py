@@ -349,9 +349,17 @@ class Reconstruct(BaseTrainer):
                 self.anomaly_z_maps, args.out_ids if bool(args.run_out) else None, getattr(args, "out_masks", None),
                 getattr(args, "pixel_bins", pixel_metrics.DEFAULT_BINS), getattr(args, "pixel_range", None) or pixel_metrics.DEFAULT_RANGE,
                 getattr(args, "pixel_thresholds", None) or pixel_metrics.DEFAULT_THRESHOLDS)
+        # --pixel_regions 1 (extension): on top of --pixel_metrics 1 the masks' connected components, the per-region
+        # overlap table and per-image component counts (ood/regions_<name>.npz).  Off without the attribute.
+        self.pixel_regions = bool(getattr(args, "pixel_regions", 0))
+        if self.pixel_regions:
+            self.px_connectivity, self.px_pro_fpr = pixel_metrics.check_region_flags(
+                self.pixel_metrics, getattr(args, "pixel_connectivity", pixel_metrics.DEFAULT_CONNECTIVITY),
+                getattr(args, "pixel_pro_fpr", pixel_metrics.DEFAULT_PRO_FPR))
         super().__init__(args)
         if not self.found_checkpoint:
             raise FileNotFoundError("Failed to find a saved model checkpoint.")
+        self.last_regions = None  # the same for --pixel_regions 1
         self.last_pixels = None  # the same for --pixel_metrics 1 (the in / out sets)
         self._px = None  # the running tables of the pass under way: hist (device), rows (host, one entry per batch)
         self._px_thr = self._px_no_mask = None  # the thresholds / an all-zero mask batch on the device
@@ -442,6 +450,7 @@ class Reconstruct(BaseTrainer):
         z_stats = zmaps.MapStats() if self.anomaly_z_maps and dataset_name == "val" else None
         self.last_pixels = None
         self._px = {"hist": None, "rows": []} if self.pixel_metrics and dataset_name != "val" else None
+        self.last_regions = None
         z_skipped = 0
         t_values = [int(t) for t in reversed(self.make_scheduler().timesteps)[1::inference_skip_factor]
                     if (self.max_t_start is None or int(t) <= int(self.max_t_start))
@@ -650,10 +659,15 @@ class Reconstruct(BaseTrainer):
             return 0
         counts, mask_pixels = self._px_batch(z.reshape(B, 2, H * W), mask)
         # one copy: each image's Z-maps travel as their int32 bit patterns with the int32 counts behind them (every bit is kept)
-        both = torch.cat([z.reshape(B, 2 * H * W).view(torch.int32), counts.reshape(B, -1)], dim=1).cpu()
+        parts = [z.reshape(B, 2 * H * W).view(torch.int32), counts.reshape(B, -1)]
+        if self.pixel_regions:  # (the component counts and the regions per image ride in the same copy)
+            components, regions = self._px_regions_batch(z.reshape(B, 2, H * W), H, W)
+            parts += [components.reshape(B, -1), regions[:, None]]
+        both = torch.cat(parts, dim=1).cpu()
         zmaps_all.append(both[:, :2 * H * W].contiguous().view(torch.float32).reshape(B, 2, H, W))
-        rows = both[:, 2 * H * W:].contiguous()
-        self._px["rows"].append(torch.cat([rows, mask_pixels.to(torch.int32)[:, None]], dim=1))
+        n_counts = counts[0].numel()
+        rows = [both[:, 2 * H * W:2 * H * W + n_counts], mask_pixels.to(torch.int32)[:, None], both[:, 2 * H * W + n_counts:]]
+        self._px["rows"].append(torch.cat(rows, dim=1))  # [counts | mask_pixels | with --pixel_regions 1: components | regions]
         return 0
 
     def _px_batch(self, z, mask):
@@ -680,7 +694,29 @@ class Reconstruct(BaseTrainer):
             zc = z[:, c].contiguous()
             ops.map_mask_hist(zc, m, self.px_lo, self.px_hi, self.px_bins, total=self._px["hist"][c])
             counts.append(ops.map_mask_counts(zc, m, self._px_thr))
+        if self.pixel_regions:
+            self._px["mask"] = m  # (for _px_regions_batch)
         return torch.stack(counts, dim=1), mask_pixels
+
+    def _px_regions_batch(self, z, H, W):
+        """--pixel_regions 1, one batch, after ``_px_batch`` (which left the batch's mask on the device): the mask's connected
+        components are labelled once; per channel one overlap call into the pass's [2, nbins + 1] float64 table and one
+        component-counts call.  Returns (components int32 [B, 2, K, 3], regions int32 [B]) on the device.  A set without masks
+        runs on the all-zero mask: 0 regions, nothing added to the table, hit = 0."""
+        B, _, P = z.shape
+        if P > ops.MAP_LABEL_MAX_PIXELS:
+            raise ValueError(f"--pixel_regions 1: maps of {H} x {W} pixels are above the {ops.MAP_LABEL_MAX_PIXELS} pixels "
+                             f"(128 x 128) a labelled plane may have")
+        m = self._px.pop("mask").reshape(B, H, W)
+        labels, regions = ops.map_label(m, self.px_connectivity)
+        if self._px.get("overlap") is None:
+            self._px["overlap"] = torch.zeros((2, self.px_bins + 1), dtype=torch.float64, device=self.device)
+        components = []
+        for c in range(2):
+            zc = z[:, c].contiguous().reshape(B, H, W)
+            ops.map_region_overlap(zc, labels, regions, self.px_lo, self.px_hi, self.px_bins, total=self._px["overlap"][c])
+            components.append(ops.map_component_counts(zc, m, labels, regions, self._px_thr, self.px_connectivity))
+        return torch.stack(components, dim=1), regions
 
     def _z_set_tables(self, stats, t_values):
         mean, inv_std = stats.finalize(self.z_std_floor)
@@ -785,10 +821,25 @@ class Reconstruct(BaseTrainer):
             if dist.get_backend() == "gloo" and hist.is_cuda:  # (the test hook of gather_scores)
                 hist = hist.cpu()
             dist.all_reduce(hist, op=dist.ReduceOp.SUM)
+        overlap = self._px.get("overlap")
+        if self.pixel_regions and self.ddp:  # (one more all_reduce: the float64 overlap table)
+            if dist.get_backend() == "gloo" and overlap.is_cuda:
+                overlap = overlap.cpu()
+            dist.all_reduce(overlap, op=dist.ReduceOp.SUM)
         got = self._gather_map_rows("--pixel_metrics 1", loader, results, local_ids, gathered_ids, name_of, self._px["rows"])
         if got is not None:
             stems, rows = got
             rows = np.rint(rows).astype(np.int64)
+            if self.pixel_regions:  # the columns behind mask_pixels: components [2, K, 3], regions
+                rows, extra = rows[:, :2 * K * 3 + 1], rows[:, 2 * K * 3 + 1:]
+                self.last_regions = {"filename": np.asarray(stems), "t": np.asarray(t_values, dtype=np.int64),
+                                     "channels": np.asarray(zmaps.CHANNELS), "lo": np.float64(self.px_lo),
+                                     "hi": np.float64(self.px_hi), "nbins": np.int64(self.px_bins),
+                                     "connectivity": np.int64(self.px_connectivity), "regions": extra[:, -1].astype(np.int32),
+                                     "overlap": overlap.cpu().numpy().astype(np.float64),
+                                     "thresholds": np.asarray(self.px_thresholds, dtype=np.float32),
+                                     "components": extra[:, :-1].reshape(-1, 2, K, 3).astype(np.int32),
+                                     "sigma": np.float64(self.z_sigma)}
             self.last_pixels = {"filename": np.asarray(stems), "t": np.asarray(t_values, dtype=np.int64),
                                 "channels": np.asarray(zmaps.CHANNELS), "lo": np.float64(self.px_lo), "hi": np.float64(self.px_hi),
                                 "nbins": np.int64(self.px_bins), "hist": hist.cpu().numpy().astype(np.int64),
@@ -840,7 +891,11 @@ class Reconstruct(BaseTrainer):
                 # filename [N], t, channels, lo, hi, nbins, hist int64 [2, 2, nbins + 1], thresholds [K], counts int32 [N, 2, K, 3],
                 # mask_pixels [N], sigma
                 np.savez(self.out_dir / f"pixels_{name}.npz", **self.last_pixels)
-        self.last_maps = self.last_zmaps = self.last_pixels = None
+            if self.pixel_regions and self.last_regions is not None:
+                # filename [N], t, channels, lo, hi, nbins, connectivity, regions int32 [N], overlap float64 [2, nbins + 1],
+                # thresholds [K], components int32 [N, 2, K, 3] = (hit, pred, false_pred), sigma
+                np.savez(self.out_dir / f"regions_{name}.npz", **self.last_regions)
+        self.last_maps = self.last_zmaps = self.last_pixels = self.last_regions = None
 
     def reconstruct(self, args):
         if bool(args.run_val):

@@ -500,6 +500,40 @@ int ddpm_map_mask_counts_f32(const float *maps, const uint8_t *masks, int N, int
                              int32_t *counts, ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Region-level evaluation of maps: connected components, region overlap, component counts (--pixel_regions 1).
+ * Entry points added without an ABI bump; no size function (the caller allocates every buffer); every pointer but the stream is a
+ * device buffer.  Planes [H, W] with 1 <= H * W <= 16 384 (128 x 128); connectivity 4 (the cross) or 8 (the 3 x 3 structure).  One
+ * workgroup per image: no communication between workgroups, no global atomics, every output element written, no buffer's
+ * previous contents read (but `total` with accumulate != 0).  Refused with -1: a larger plane, a null pointer, another
+ * connectivity, an output that overlaps another operand.
+ * ---------------------------------------------------------------------------------- */
+/* Connected components of the pixels with mask != 0.  labels [N, H, W] (int32): 0 outside, else 1 .. R, the components of an
+ * image numbered in ascending order of their smallest flat pixel index (the numbering of scipy.ndimage.label); regions [N]: R.
+ * An image's result depends on nothing but the image: not on N, not on its place in the batch, not on what labels / regions
+ * held.  Union-find in LDS with bounded loops; regions[n] = -1 would report a bound that ran out (it cannot).               */
+int ddpm_map_label_u8(const uint8_t *masks, int N, int H, int W, int connectivity, int32_t *labels, int32_t *regions,
+                      ddpm_stream_t stream);
+/* The same for the pixels with v > thr (a NaN pixel, or a NaN thr: outside).                                                */
+int ddpm_map_label_f32(const float *maps, float thr, int N, int H, int W, int connectivity, int32_t *labels, int32_t *regions,
+                       ddpm_stream_t stream);
+/* Per-region overlap of maps [N, P] with the labelled regions (labels [N, P], regions [N] as ddpm_map_label_* leave them; a label
+ * outside 1 .. regions[n] belongs to no region).  The bin of a value is that of ddpm_map_mask_hist_f32, NaN in column nbins.
+ *   scratch[n, b] = w_n[b] = sum over r = 1 .. R_n, ascending, of (double)h_{n,r}[b] / (double)area_{n,r},
+ * h the region's integer histogram and area the count of all its pixels, NaN ones included; then, in a second launch,
+ *   total[b] = (accumulate ? total[b] : 0) + w_0[b] + w_1[b] + ..., one addition per image in ascending n.
+ * Hence two consecutive calls over the halves of a batch (the second with accumulate = 1) leave the bits one call over the
+ * whole batch leaves.  Divisions and additions only: nothing to contract.  scratch: N (nbins + 1) doubles, total: nbins + 1.
+ * One pass over the plane per region: fast for the handful of regions of a mask, correct for any number.                    */
+int ddpm_map_region_overlap_f32(const float *maps, const int32_t *labels, const int32_t *regions, int N, int P, float lo,
+                                float inv_step, int nbins, double *scratch, double *total, int accumulate, ddpm_stream_t stream);
+/* counts [N, K, 3] (int32) per image and threshold: hit = the ground-truth regions (labels / regions) with at least one pixel
+ * v > thr; pred = the connected components of {v > thr}; false_pred = those components without a pixel of mask != 0.
+ * thresholds: [K] fp32 on the device, 1 <= K <= 8.  One workgroup per (image, threshold).                                    */
+int ddpm_map_component_counts_f32(const float *maps, const uint8_t *masks, const int32_t *labels, const int32_t *regions, int N,
+                                  int H, int W, const float *thresholds, int K, int connectivity, int32_t *counts,
+                                  ddpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Loss terms of VQ-VAE training (src/trainers/vqvae_trainer.py: 0.001 x PerceptualLoss + JukeboxLoss in the generator loss;
  * SURVEY.md A.8).  Entry points added without an ABI bump.  Everything is deterministic (fixed-order sums, no atomics).
  * ---------------------------------------------------------------------------------- */

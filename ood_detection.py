@@ -26,6 +26,11 @@ def parse_args(argv=None):
                    help="--score zmap / pixel: which Z-map")
     p.add_argument("--pixel_include_in", type=int, default=0,
                    help="--score pixel: 1 pools the in set's pixels (pixels_in.npz) into the negatives")
+    p.add_argument("--pixel_regions", type=int, default=0,
+                   help="--score pixel: 1 also reads the regions_*.npz files of reconstruct.py --pixel_regions 1 and prints the "
+                        "region-overlap score (AUPRO) and, per fixed threshold, region recall, component precision and their F1")
+    p.add_argument("--pixel_pro_fpr", type=float, default=0.3,
+                   help="--score pixel --pixel_regions 1: the false-positive rate up to which the region-overlap curve is integrated")
     p.add_argument("--zmap_reduce", default="mean", choices=["mean", "max"], help="--score zmap: mean or maximum over the pixels")
     return p.parse_args(argv)
 

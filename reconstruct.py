@@ -72,6 +72,10 @@ _EXTENSIONS = [
                              "with 'masks', a one-row CSV of mask files, or empty for a set without masks (all zero)"),
     ("pixel_bins", int, 4096, "--pixel_metrics 1: bins of the histogram (1 .. 8191)"),
     ("pixel_thresholds", str, "2,3,4", "--pixel_metrics 1: comma list of 1 .. 8 fixed Z thresholds of the per-image Dice"),
+    ("pixel_regions", int, 0, "1 (with --pixel_metrics 1): also write ood/regions_<name>.npz, the masks' connected components "
+                              "against the Z-maps: the per-region overlap table (AUPRO) and per-image component counts at the "
+                              "fixed thresholds (ood_detection.py --score pixel --pixel_regions 1); planes up to 128 x 128"),
+    ("pixel_pro_fpr", float, 0.3, "--pixel_regions 1: the false-positive rate up to which the region-overlap curve is integrated"),
 ]
 
 
@@ -90,6 +94,8 @@ def build_parser():
         ext.add_argument(f"--{name}", **kw)
     ext.add_argument("--pixel_range", type=float, nargs=2, default=[-16.0, 48.0], metavar=("LO", "HI"),
                      help="--pixel_metrics 1: the Z range the bins divide; values outside fall into the first / last bin")
+    ext.add_argument("--pixel_connectivity", type=int, default=8, choices=[8, 4],
+                     help="--pixel_regions 1: the neighbours that join two pixels (8: the 3 x 3 structure, 4: the cross)")
     ext.add_argument("--timestep_list", default="monai", choices=["monai", "diffusers"],
                      help="100-entry or 101-entry PLMS timestep list (Q9)")
     return parser
