@@ -1,12 +1,13 @@
 // Per-pixel Z-scores of the anomaly maps against the validation set (only with --anomaly_z_maps 1).
 //   map_stats_update   running per-column mean and sum of squared deviations over the validation set, one batch per call
 //   map_zscore         out[b, p] = weight * sum_t (v[b, t, p] - mean[t, p]) * inv_std[t, p]
+//   map_zscore_loo     the same for a row of the validation set itself, against the statistics of the OTHER n - 1 rows
 //   map_blur           separable Gaussian smoothing of [N, H, W] maps, scipy's mode="reflect" boundary, one launch
 // Plain fp32, no atomics, no cross-thread reductions: every output value is ONE fixed sequence of operations (the build has no FMA
-// contraction, so each operation rounds once).  map_stats_update and map_zscore: a thread owns V adjacent columns (V = 4: 16-byte
+// contraction, so each operation rounds once).  map_stats_update, map_zscore and map_zscore_loo: a thread owns V adjacent columns (V = 4: 16-byte
 // accesses when the row length is a multiple of 4 and every base is 16-byte aligned; V = 1: the scalar path); both forms do the
 // same arithmetic per column, so they give the same bits.  Bytes per column: stats 4 B + 16 (the second pass over the column
-// is served from cache), zscore 4 n_t (B + 2) / B + 4 per output.
+// is served from cache), zscore and zscore_loo 4 n_t (B + 2) / B + 4 per output (the tables are re-read from cache across the B rows).
 // map_blur: a workgroup of 256 threads owns a 32 x 32 output tile.  It stages the tile plus a halo of `radius` on all four sides
 // through refl() into LDS ((32 + 2 r)^2 floats), runs the H pass over the tile's rows and tile width plus halo in W into a
 // second LDS array (32 x (32 + 2 r) floats) and the W pass from there to `out`.  radius <= kBlurMaxRadius = 16:
@@ -167,6 +168,76 @@ int launch_map_zscore(const float *values, const float *mean, const float *inv_s
   return 0;
 }
 
+// ---- leave-one-out Z-map of a validation row ------------------------------------------------------------------------------------------
+// The row was counted in (n, mean, m2); taking it out again has a closed form per column:
+//   d = v - mean;  dl = d * r1 (= v - the mean of the others);  q = max(m2 - d * dl, 0) (= the others' M2);  s = sqrt(q * r2)
+// with r1 = n / (n - 1) and r2 = 1 / (n - 2) formed by the launcher in float64 and rounded once.  The divisor is floored at
+// floor[t, c], one number per (t-start, channel): a thread's V columns lie in one channel (plane % V == 0), so it is one scalar
+// per t.  fmaxf drops a NaN operand, but a NaN value is still in dl, the numerator: NaN in, NaN out.
+template <int V>
+__global__ __launch_bounds__(256) void map_zscore_loo_kernel(const float *__restrict__ values, const float *__restrict__ mean,
+                                                             const float *__restrict__ m2, const float *__restrict__ floor,
+                                                             float *__restrict__ out, int n_t, int64_t plane, int64_t items,
+                                                             float r1, float r2, float weight) {
+  struct alignas(4 * V) Vec { float v[V]; };
+  const int64_t P1 = 2 * plane;
+  const int64_t per_row = P1 / V;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += stride) {
+    const int64_t bi = i / per_row, p = (i - bi * per_row) * V;
+    const int c = p >= plane ? 1 : 0;
+    const float *pv = values + bi * n_t * P1 + p;
+    float acc[V];
+    for (int t = 0; t < n_t; ++t) {
+      const Vec x = *reinterpret_cast<const Vec *>(pv + (int64_t)t * P1);
+      const Vec m = *reinterpret_cast<const Vec *>(mean + (int64_t)t * P1 + p);
+      const Vec Q = *reinterpret_cast<const Vec *>(m2 + (int64_t)t * P1 + p);
+      const float fl = floor[2 * t + c];
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float d = x.v[j] - m.v[j];
+        const float dl = d * r1;
+        const float q = fmaxf(Q.v[j] - d * dl, 0.f);
+        const float sd = sqrtf(q * r2);
+        const float z = dl / fmaxf(sd, fl);
+        acc[j] = t == 0 ? z : acc[j] + z;
+      }
+    }
+    Vec o;
+#pragma unroll
+    for (int j = 0; j < V; ++j) o.v[j] = acc[j] * weight;
+    *reinterpret_cast<Vec *>(out + bi * P1 + p) = o;
+  }
+}
+
+int launch_map_zscore_loo(const float *values, const float *mean, const float *m2, const float *floor, float *out, int B, int n_t,
+                          int64_t plane, int64_t n, float weight, hipStream_t s) {
+  DDPM_CHECK_ARG(values && mean && m2 && floor && out, "map_zscore_loo: null pointer");
+  DDPM_CHECK_ARG(B > 0, "map_zscore_loo: B must be positive (got %d)", B);
+  DDPM_CHECK_ARG(n_t > 0, "map_zscore_loo: n_t must be positive (got %d)", n_t);
+  DDPM_CHECK_ARG(plane > 0, "map_zscore_loo: plane must be positive (got %lld)", (long long)plane);
+  DDPM_CHECK_ARG(n >= 3 && n < ((int64_t)1 << 52),
+                 "map_zscore_loo: the statistics of the other rows need n >= 3 rows (got %lld)", (long long)n);
+  DDPM_CHECK_ARG((double)B * n_t * 2.0 * (double)plane < 9.0e18, "map_zscore_loo: tensor too large");
+  const int64_t P1 = 2 * plane;
+  const double o_bytes = 4.0 * B * (double)P1, t_bytes = 4.0 * n_t * (double)P1, f_bytes = 8.0 * n_t;
+  DDPM_CHECK_ARG(!zm_overlap(out, o_bytes, values, t_bytes * B) && !zm_overlap(out, o_bytes, mean, t_bytes) &&
+                     !zm_overlap(out, o_bytes, m2, t_bytes) && !zm_overlap(out, o_bytes, floor, f_bytes),
+                 "map_zscore_loo: out aliases an input");
+  const float r1 = (float)((double)n / (double)(n - 1)), r2 = (float)(1.0 / (double)(n - 2));
+  const bool vec = (plane & 3) == 0 && (((uintptr_t)values | (uintptr_t)mean | (uintptr_t)m2 | (uintptr_t)out) & 15) == 0;
+  const int64_t items = vec ? (int64_t)B * (P1 / 4) : (int64_t)B * P1;
+  ProfScope prof(s, "map_zscore_loo", 8.0 * B * n_t * (double)P1, t_bytes * (B + 2) + o_bytes + f_bytes);
+  if (vec)
+    hipLaunchKernelGGL(map_zscore_loo_kernel<4>, dim3(zm_blocks(items)), dim3(256), 0, s, values, mean, m2, floor, out, n_t, plane,
+                       items, r1, r2, weight);
+  else
+    hipLaunchKernelGGL(map_zscore_loo_kernel<1>, dim3(zm_blocks(items)), dim3(256), 0, s, values, mean, m2, floor, out, n_t, plane,
+                       items, r1, r2, weight);
+  DDPM_CHECK_LAUNCH();
+  return 0;
+}
+
 // ---- separable Gaussian smoothing, reflect boundary ------------------------------------------------------------------------------------
 constexpr int kBlurTile = 32, kBlurMaxRadius = 16;
 constexpr int kBlurSpan = kBlurTile + 2 * kBlurMaxRadius;  // 64: the widest staged extent
@@ -249,6 +320,11 @@ extern "C" int ddpm_map_stats_update_f32(const float *values, int B, int64_t P, 
 extern "C" int ddpm_map_zscore_f32(const float *values, const float *mean, const float *inv_std, float *out, int B, int n_t,
                                    int64_t P1, float weight, ddpm_stream_t stream) {
   return launch_map_zscore(values, mean, inv_std, out, B, n_t, P1, weight, as_stream(stream));
+}
+
+extern "C" int ddpm_map_zscore_loo_f32(const float *values, const float *mean, const float *m2, const float *floor, float *out,
+                                       int B, int n_t, int64_t plane, int64_t n, float weight, ddpm_stream_t stream) {
+  return launch_map_zscore_loo(values, mean, m2, floor, out, B, n_t, plane, n, weight, as_stream(stream));
 }
 
 extern "C" int ddpm_map_blur_f32(const float *in, float *out, const float *taps, int radius, int N, int H, int W,

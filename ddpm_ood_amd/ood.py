@@ -191,9 +191,67 @@ def score_pixels(out_npz, in_npz=None, key: str = "z_mse_map", regions_npz=None,
     return out
 
 
+def _need(path, flag):
+    path = Path(path)
+    if not path.exists():
+        raise FileNotFoundError(f"no {path}: reconstruct.py {flag} writes it")
+    return np.load(path)
+
+
+def score_pixels_calibrated(out_dir, out_name, key: str = "z_mse_map", regions: bool = False):
+    """The operating points calibrated on the validation set (``reconstruct.py --pixel_calibrate_fpr``) for one out
+    set and the Z-map ``key``: a list, one dict per target rate, of ``fpr`` (the target), ``threshold``, ``val_fpr`` (the rate the
+    threshold reaches on the validation set's leave-one-out Z-maps, from calibration.npz), ``in_fpr`` (the rate on the in set) and
+    ``pooled_dice`` (both exact sums over the histograms of pixels_in.npz / pixels_<name>.npz from the threshold's bin on),
+    ``mean_dice`` (the mean per-image Dice, calibrated_<name>.npz) and with ``regions`` region_recall, component_precision and
+    component_f1 (calibrated_<name>.npz beside the region counts of regions_<name>.npz).  A missing file is a
+    FileNotFoundError that names the reconstruct flag that writes it."""
+    from . import pixel_metrics as pm
+
+    if key not in pm.KEYS:
+        raise ValueError(f"score_pixels_calibrated: key must be one of {pm.KEYS}, got {key!r}")
+    c = pm.KEYS.index(key)
+    out_dir = Path(out_dir)
+    cal = pm.load_calibration(out_dir / pm.CALIBRATION_FILE)
+    px_out = _need(out_dir / f"pixels_{out_name}.npz", pm.FLAG)
+    px_in = _need(out_dir / "pixels_in.npz", pm.FLAG)
+    done = _need(out_dir / f"calibrated_{out_name}.npz", f"{pm.CALIBRATE_FLAG} with {pm.FLAG}")
+    grid = (float(cal["lo"]), float(cal["hi"]), int(cal["nbins"]))
+    for name, z in ((f"pixels_{out_name}.npz", px_out), ("pixels_in.npz", px_in)):
+        if (float(z["lo"]), float(z["hi"]), int(z["nbins"])) != grid:
+            raise ValueError(f"score_pixels_calibrated: {name} has another range or another number of bins than {pm.CALIBRATION_FILE}")
+    if not np.array_equal(np.asarray(done["thresholds"]), np.asarray(cal["thresholds"])):
+        raise ValueError(f"score_pixels_calibrated: calibrated_{out_name}.npz was counted at other thresholds than {pm.CALIBRATION_FILE} holds")
+    ks = [int(k) for k in cal["bin"][c]]
+    h_out = np.asarray(px_out["hist"])[c][:, :-1].astype(np.float64)
+    h_in = np.asarray(px_in["hist"])[c][:, :-1].astype(np.float64).sum(axis=0)  # (an in set has no anomaly: every pixel a negative)
+    val_fpr = pm.reached_fpr(cal["hist"][c], ks)
+    mean_dice = pm.dice_from_counts(np.asarray(done["counts"])[:, c]).mean(axis=0)
+    comp = None
+    if regions:
+        if "components" not in done.files:
+            raise FileNotFoundError(f"calibrated_{out_name}.npz holds no component counts: reconstruct.py {pm.REGION_FLAG} with "
+                                    f"{pm.CALIBRATE_FLAG} writes them")
+        reg = _need(out_dir / f"regions_{out_name}.npz", pm.REGION_FLAG)
+        comp = pm.component_scores(np.asarray(done["components"])[:, c], np.asarray(reg["regions"]))
+    rows = []
+    for j, k in enumerate(ks):
+        tp, fp = h_out[1, k:].sum(), h_out[0, k:].sum()
+        fn = h_out[1].sum() - tp
+        den = 2.0 * tp + fp + fn
+        row = {"fpr": float(cal["fpr"][j]), "threshold": float(cal["thresholds"][c, j]), "val_fpr": float(val_fpr[j]),
+               "in_fpr": float(h_in[k:].sum() / h_in.sum()) if h_in.sum() > 0 else float("nan"),
+               "pooled_dice": float(2.0 * tp / den) if den > 0 else 1.0, "mean_dice": float(mean_dice[j])}
+        if comp is not None:
+            row.update({name: float(comp[name][j]) for name in ("region_recall", "component_precision", "component_f1")})
+        rows.append(row)
+    return rows
+
+
 def main_pixels(args, out_data=None):
     """``ood_detection.py --score pixel``: per out set the pixel AUROC, AP, best Dice and the mean per-image Dice at the fixed
-    thresholds, from pixels_<name>.npz (and pixels_in.npz with --pixel_include_in 1)."""
+    thresholds, from pixels_<name>.npz (and pixels_in.npz with --pixel_include_in 1).  --pixel_calibrated 1: also the operating
+    points of ``score_pixels_calibrated``."""
     model = args.model_name
     run_dir = Path(args.output_dir) / model
     print(f"Run directory: {str(run_dir)}")
@@ -220,6 +278,15 @@ def main_pixels(args, out_data=None):
             for t in s["region_recall"]:
                 print(f"Regions for {model} vs {o} at Z > {t:g}: recall {s['region_recall'][t]:.4f}, component precision "
                       f"{s['component_precision'][t]:.4f}, F1 {s['component_f1'][t]:.4f}")
+        if bool(getattr(args, "pixel_calibrated", 0)):
+            s["calibrated"] = score_pixels_calibrated(out_dir, o, key, regions)
+            for r in s["calibrated"]:
+                print(f"Calibrated for {model} vs {o} at validation FPR <= {r['fpr']:g}: Z > {r['threshold']:.4f} (validation FPR "
+                      f"{r['val_fpr']:.5f}, in-set FPR {r['in_fpr']:.5f}), pooled Dice {r['pooled_dice']:.4f}, mean image Dice "
+                      f"{r['mean_dice']:.4f}")
+                if regions:
+                    print(f"Calibrated regions for {model} vs {o} at validation FPR <= {r['fpr']:g}: recall {r['region_recall']:.4f}, "
+                          f"component precision {r['component_precision']:.4f}, F1 {r['component_f1']:.4f}")
     return got
 
 

@@ -821,6 +821,32 @@ def map_zscore(values, mean, inv_std, weight: float = None, out=None):
     return out
 
 
+def map_zscore_loo(values, mean, m2, n: int, floor, weight: float = None, out=None):
+    """The leave-one-out Z-maps of rows of the validation set: ``values`` [B, n_t, 2, *plane] are rows that were
+    counted in the full set's statistics ``mean`` / ``m2`` [n_t, 2, *plane] over ``n`` rows; each is normalised by the mean and the
+    sample standard deviation (ddof = 1) of the OTHER n - 1 rows, the divisor floored at ``floor`` [n_t, 2], and averaged over
+    the t-starts (``weight`` defaults to 1 / n_t).  Returns fp32 [B, 2, *plane]; ``out``: a contiguous fp32 tensor of that shape to
+    write into (it may overlap no input).  n >= 3, else ValueError.  Every operand is a contiguous fp32 tensor on one ROCm
+    device (ValueError otherwise: no CPU fallback)."""
+    lib = _lib.load()
+    for name, t in (("values", values), ("mean", mean), ("m2", m2), ("floor", floor)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() \
+                or t.device != values.device:
+            raise ValueError(f"map_zscore_loo: {name} must be a contiguous float32 tensor on one ROCm device (no CPU fallback)")
+    if values.ndim < 4 or values.shape[2] != 2 or mean.shape != values.shape[1:] or m2.shape != mean.shape \
+            or tuple(floor.shape) != tuple(values.shape[1:3]) or values.numel() == 0:
+        raise ValueError(f"map_zscore_loo wants values [B, n_t, 2, *plane], two tables [n_t, 2, *plane] and floor [n_t, 2], got "
+                         f"{tuple(values.shape)}, {tuple(mean.shape)}, {tuple(m2.shape)} and {tuple(floor.shape)}")
+    if int(n) != n or int(n) < 3:
+        raise ValueError(f"map_zscore_loo: the statistics of the other rows need n >= 3 rows, got {n}")
+    B, n_t = values.shape[:2]
+    out = _fresh_out(out, (B,) + tuple(values.shape[2:]), values.device, "map_zscore_loo")
+    w = 1.0 / n_t if weight is None else float(weight)
+    check(lib.ddpm_map_zscore_loo_f32(ptr(values), ptr(mean), ptr(m2), ptr(floor), ptr(out), B, n_t,
+                                      int(np.prod(values.shape[3:], dtype=np.int64)), int(n), w, stream_ptr()), "map_zscore_loo")
+    return out
+
+
 def gaussian_taps(sigma: float, truncate: float = 4.0):
     """The weights of ``scipy.ndimage.gaussian_filter`` (order 0) in float64: exp(-k^2 / 2 sigma^2) for |k| <= radius =
     int(truncate * sigma + 0.5), normalised to sum 1.  sigma <= 0 or radius 0: the single weight 1."""

@@ -144,6 +144,141 @@ def check_flags(anomaly_z_maps, out_ids, out_masks=None, bins=DEFAULT_BINS, valu
     return lo, hi, nbins, thr, masks
 
 
+# ---- thresholds calibrated on the validation set (``--pixel_calibrate_fpr``) -------------------------
+# The validation set's leave-one-out Z-maps (``ops.map_zscore_loo``) are binned like every other set's; a threshold is the bin edge
+# above which at most a fraction f of those healthy pixels falls.  Bin edges on purpose: the pooled TP / FP / FN at a calibrated
+# threshold, and its realised false-positive rate on the in set, are sums over the histograms pixels_<name>.npz already holds.
+
+CALIBRATE_FLAG = "--pixel_calibrate_fpr"
+BUDGET_FLAG = "--pixel_calibrate_budget_gb"
+CALIBRATION_FILE = "calibration.npz"
+DEFAULT_BUDGET_GB = 8.0
+
+
+def thresholds_from_hist(hist_negatives, lo: float, hi: float, fprs):
+    """(bin indices int64 [F], thresholds float64 [F]) from the histogram [nbins + 1] of healthy pixels (the last column, the NaN
+    pixels, is left out): with c_k the pixels of bins >= k and N the scored pixels, k* is the smallest k with c_k / N <= f and the
+    threshold lo + k* step.  k* = nbins (more than f of the pixels lie in the last bin, which takes everything from hi on) is a
+    ValueError that names --pixel_range, as are an empty histogram, a target outside (0, 1) and other than 1 .. 8 targets."""
+    h = np.asarray(hist_negatives)
+    if h.ndim != 1 or h.shape[0] < 2:
+        raise ValueError(f"thresholds_from_hist wants one histogram [nbins + 1] (the last column the NaN pixels), got {h.shape}")
+    if (h < 0).any():
+        raise ValueError("a histogram holds counts: negative entry")
+    f = np.asarray(fprs, dtype=np.float64).reshape(-1)
+    if not 1 <= len(f) <= MAX_THRESHOLDS:
+        raise ValueError(f"{CALIBRATE_FLAG} takes 1 .. {MAX_THRESHOLDS} target rates, got {len(f)}")
+    if not all(0.0 < v < 1.0 for v in f):
+        raise ValueError(f"{CALIBRATE_FLAG}: every target false-positive rate must lie in (0, 1), got {f.tolist()}")
+    nbins = h.shape[0] - 1
+    scored = h[:-1].astype(np.int64)
+    N = int(scored.sum())
+    if N == 0:
+        raise ValueError(f"{CALIBRATE_FLAG}: the validation histogram holds no scored pixel: nothing to calibrate on")
+    above = np.concatenate([np.cumsum(scored[::-1])[::-1], [0]]).astype(np.float64) / N  # c_k / N, k = 0 .. nbins (not increasing)
+    ks = np.asarray([int(np.argmax(above <= v)) for v in f], dtype=np.int64)
+    if (ks >= nbins).any():
+        worst = float(f[ks >= nbins].min())
+        raise ValueError(f"{CALIBRATE_FLAG}: more than {worst:g} of the validation pixels lie in the last bin (Z >= "
+                         f"{float(lo) + (nbins - 1) * (float(hi) - float(lo)) / nbins:g}): no bin edge reaches that rate; widen "
+                         f"--pixel_range beyond {hi:g}")
+    return ks, float(lo) + ks * ((float(hi) - float(lo)) / nbins)
+
+
+def reached_fpr(hist_negatives, ks):
+    """c_k / N of ``thresholds_from_hist`` at the bin indices ``ks``: the rate a calibrated threshold reaches on that histogram."""
+    scored = np.asarray(hist_negatives)[..., :-1].astype(np.float64)
+    return np.asarray([scored[..., int(k):].sum() for k in np.asarray(ks).reshape(-1)]) / scored.sum()
+
+
+def parse_fprs(text):
+    """"0.05,0.01" (or a sequence of numbers) -> [0.05, 0.01]; 1 .. 8 targets, each in (0, 1)."""
+    if isinstance(text, str):
+        text = [s for s in text.split(",") if s.strip()]
+    try:
+        f = [float(v) for v in text]
+    except (TypeError, ValueError):
+        raise ValueError(f"{CALIBRATE_FLAG} must be a comma list of numbers, got {text!r}") from None
+    if not 1 <= len(f) <= MAX_THRESHOLDS:
+        raise ValueError(f"{CALIBRATE_FLAG} takes 1 .. {MAX_THRESHOLDS} target rates, got {len(f)}")
+    if not all(0.0 < v < 1.0 for v in f):
+        raise ValueError(f"{CALIBRATE_FLAG}: every target false-positive rate must lie in (0, 1), got {f}")
+    return f
+
+
+def check_calibration_flags(anomaly_z_maps, fprs, budget_gb=DEFAULT_BUDGET_GB):
+    """What ``Reconstruct`` refuses at construction when ``--pixel_calibrate_fpr`` is given (no device needed).  Returns (the
+    target rates, the budget in bytes)."""
+    if not anomaly_z_maps:
+        raise ValueError(f"{CALIBRATE_FLAG} calibrates thresholds of the Z-maps: it needs --anomaly_z_maps 1")
+    try:
+        budget = float(budget_gb)
+    except (TypeError, ValueError):
+        raise ValueError(f"{BUDGET_FLAG} is a number of GiB, got {budget_gb!r}") from None
+    if not budget > 0 or not np.isfinite(budget):
+        raise ValueError(f"{BUDGET_FLAG} must be a positive number of GiB, got {budget_gb}")
+    return parse_fprs(fprs), int(budget * (1 << 30))
+
+
+def check_budget(rows: int, n_t: int, H: int, W: int, budget_bytes: int):
+    """The bytes of the validation rows a rank keeps on the device for the leave-one-out pass (rows x n_t x 2 x H x W fp32), or
+    ValueError when they exceed the budget."""
+    need = int(rows) * int(n_t) * 2 * int(H) * int(W) * 4
+    if need > int(budget_bytes):
+        raise ValueError(f"{CALIBRATE_FLAG}: keeping the per-t maps of {rows} validation images ({rows} x {n_t} x 2 x {H} x {W} fp32 "
+                         f"= {need / (1 << 30):.3f} GiB on this rank) exceeds the budget of {budget_bytes / (1 << 30):.3f} GiB: raise "
+                         f"{BUDGET_FLAG}, use more ranks or truncate the set with --first_n_val")
+    return need
+
+
+CALIBRATION_KEYS = ("t", "n", "fpr", "bin", "thresholds", "hist", "lo", "hi", "nbins", "sigma", "rel_floor", "channels")
+
+
+def calibration_tables(hist, t_values, n, fprs, lo, hi, nbins, sigma, rel_floor):
+    """The contents of ood/calibration.npz from the validation set's histogram int64 [2, nbins + 1] (one row per channel)."""
+    hist = np.asarray(hist).astype(np.int64)
+    if hist.shape != (2, int(nbins) + 1):
+        raise ValueError(f"a calibration histogram is [2, nbins + 1] (one row per channel), got {hist.shape} for nbins = {nbins}")
+    got = [thresholds_from_hist(hist[c], lo, hi, fprs) for c in range(2)]
+    return {"t": np.asarray([int(t) for t in t_values], dtype=np.int64), "n": np.int64(n), "fpr": np.asarray(fprs, dtype=np.float64),
+            "bin": np.stack([g[0] for g in got]).astype(np.int64), "thresholds": np.stack([g[1] for g in got]).astype(np.float32),
+            "hist": hist, "lo": np.float64(lo), "hi": np.float64(hi), "nbins": np.int64(nbins), "sigma": np.float64(sigma),
+            "rel_floor": np.float64(rel_floor), "channels": np.asarray(CHANNELS)}
+
+
+def load_calibration(path, t_values=None, lo=None, hi=None, nbins=None, sigma=None, rel_floor=None, fprs=None):
+    """The dict of a ``calibration.npz``.  Each of the run's settings that is given must equal the file's, else ValueError; a
+    missing file is a FileNotFoundError that names the flag that writes it."""
+    from pathlib import Path
+
+    path = Path(path)
+    if not path.exists():
+        raise FileNotFoundError(f"no {path}: reconstruct.py {CALIBRATE_FLAG} (with --run_val 1) writes it")
+    with np.load(path) as z:
+        missing = [k for k in CALIBRATION_KEYS if k not in z.files]
+        if missing:
+            raise ValueError(f"{path} lacks {missing}: no calibration file")
+        cal = {k: z[k] for k in CALIBRATION_KEYS}
+    F = len(cal["fpr"])
+    if cal["bin"].shape != (2, F) or cal["thresholds"].shape != (2, F) or cal["hist"].shape != (2, int(cal["nbins"]) + 1):
+        raise ValueError(f"{path}: tables of {cal['bin'].shape}, {cal['thresholds'].shape} and {cal['hist'].shape} for {F} targets "
+                         f"and {int(cal['nbins'])} bins are no calibration")
+    if t_values is not None and [int(t) for t in t_values] != [int(t) for t in cal["t"]]:
+        raise ValueError(f"{path} was calibrated on the t-starts {[int(t) for t in cal['t']]}, this run has {[int(t) for t in t_values]}")
+    if (lo is not None and float(lo) != float(cal["lo"])) or (hi is not None and float(hi) != float(cal["hi"])):
+        raise ValueError(f"{path} holds the range [{float(cal['lo'])}, {float(cal['hi'])}), this run's --pixel_range is [{lo}, {hi})")
+    if nbins is not None and int(nbins) != int(cal["nbins"]):
+        raise ValueError(f"{path} holds {int(cal['nbins'])} bins, this run's --pixel_bins is {nbins}")
+    if sigma is not None and float(sigma) != float(cal["sigma"]):
+        raise ValueError(f"{path} was calibrated with --anomaly_z_sigma {float(cal['sigma'])}, this run has {sigma}")
+    if rel_floor is not None and float(rel_floor) != float(cal["rel_floor"]):
+        raise ValueError(f"{path} was calibrated with --anomaly_z_std_floor {float(cal['rel_floor'])}, this run has {rel_floor}")
+    if fprs is not None and [float(v) for v in fprs] != [float(v) for v in cal["fpr"]]:
+        raise ValueError(f"{path} holds the target rates {[float(v) for v in cal['fpr']]}, this run's {CALIBRATE_FLAG} is "
+                         f"{[float(v) for v in fprs]}")
+    return cal
+
+
 # ---- region-level metrics (``--pixel_regions 1``; DESIGN 3.24) ----------------------------------------------------
 # The device side (``ops.map_label`` / ``map_region_overlap`` / ``map_component_counts``) leaves the number of ground-truth
 # regions per image, the overlap table float64 [nbins + 1] = sum over the regions of (the region's pixels in the bin) / (its

@@ -356,9 +356,28 @@ class Reconstruct(BaseTrainer):
             self.px_connectivity, self.px_pro_fpr = pixel_metrics.check_region_flags(
                 self.pixel_metrics, getattr(args, "pixel_connectivity", pixel_metrics.DEFAULT_CONNECTIVITY),
                 getattr(args, "pixel_pro_fpr", pixel_metrics.DEFAULT_PRO_FPR))
+        # --pixel_calibrate_fpr F1,F2,... (extension): thresholds above which those fractions of the validation set's
+        # leave-one-out Z-map pixels fall (ood/calibration.npz), and the in / out sets' counts at them (ood/calibrated_<name>.npz).
+        # Off without the attribute.
+        self.px_calibrate = bool(getattr(args, "pixel_calibrate_fpr", None))
+        if self.px_calibrate:
+            self.cal_fprs, self.cal_budget = pixel_metrics.check_calibration_flags(
+                self.anomaly_z_maps, args.pixel_calibrate_fpr, getattr(args, "pixel_calibrate_budget_gb", pixel_metrics.DEFAULT_BUDGET_GB))
+            if not self.pixel_metrics:  # (the bins of the validation histogram are those of --pixel_range / --pixel_bins)
+                self.px_lo, self.px_hi, self.px_bins = pixel_metrics.check_flags(
+                    True, None, None, getattr(args, "pixel_bins", pixel_metrics.DEFAULT_BINS),
+                    getattr(args, "pixel_range", None) or pixel_metrics.DEFAULT_RANGE)[:3]
         super().__init__(args)
         if not self.found_checkpoint:
             raise FileNotFoundError("Failed to find a saved model checkpoint.")
+        self.last_calibration = None  # the contents of ood/calibration.npz after a validation pass with --pixel_calibrate_fpr
+        self.last_calibrated = None  # the same for ood/calibrated_<name>.npz (the in / out sets)
+        self._cal = None  # the calibration in force: the file's dict and "thr", the thresholds [2, F] on the device
+        self._cal_rows = None  # the validation pass under way: the counted rows' per-t maps, one device tensor per batch
+        # test hook (not a CLI flag): keep the retained validation rows and their leave-one-out Z-maps on the host after the
+        # pass (``calibration_rows`` [n, n_t, 2, H, W], ``calibration_zmaps`` [n, 2, H, W]; this rank's rows in the pass's order)
+        self.keep_calibration_rows = bool(getattr(args, "keep_calibration_rows", False))
+        self.calibration_rows = self.calibration_zmaps = None
         self.last_regions = None  # the same for --pixel_regions 1
         self.last_pixels = None  # the same for --pixel_metrics 1 (the in / out sets)
         self._px = None  # the running tables of the pass under way: hist (device), rows (host, one entry per batch)
@@ -445,7 +464,7 @@ class Reconstruct(BaseTrainer):
         pl = self._perceptual()
         self.model.eval()
         ids_all, names_all, scores_all, maps_all, zmaps_all = [], [], [], [], []
-        self.last_maps = self.last_zmaps = None
+        self.last_maps = self.last_zmaps = self.last_calibrated = None
         # --anomaly_z_maps 1: the validation pass accumulates the per-pixel statistics, every other pass is normalised by them
         z_stats = zmaps.MapStats() if self.anomaly_z_maps and dataset_name == "val" else None
         self.last_pixels = None
@@ -455,6 +474,11 @@ class Reconstruct(BaseTrainer):
         t_values = [int(t) for t in reversed(self.make_scheduler().timesteps)[1::inference_skip_factor]
                     if (self.max_t_start is None or int(t) <= int(self.max_t_start))
                     and (self.t_start_subset is None or int(t) in set(self.t_start_subset))]
+        self._cal_rows = None
+        if self.px_calibrate and z_stats is not None:  # the counted rows stay on the device for the leave-one-out pass: refuse first
+            shape = tuple(loader.images[0].shape) if len(loader.names) else (0, 0)
+            pixel_metrics.check_budget(len(loader.names), len(t_values), shape[-2], shape[-1], self.cal_budget)
+            self._cal_rows = []
         n_recon = n_fwd = 0
         guard = {"batches_rerun_fp32": 0, "batches_nonfinite": 0}
         _lib.status_read(clear=True)  # whatever an earlier caller left behind is not this run's
@@ -527,6 +551,8 @@ class Reconstruct(BaseTrainer):
             self.last_stats["zmap_rows_skipped"] = z_skipped
             if z_stats is not None:
                 self._z_finish_validation(loader, z_stats, t_values)
+                if self.px_calibrate:
+                    self._cal_finish_validation(self.last_map_stats[0], t_values)
         return self._collect(loader, dataset_name, t_values, ids_all, names_all, scores_all, quiet, maps_all, zmaps_all)
 
     def _score_batch(self, batch, pl, inference_skip_factor):
@@ -640,10 +666,11 @@ class Reconstruct(BaseTrainer):
         if z_stats is not None:
             finite = torch.isfinite(scores).all(dim=2).all(dim=1)
             keep = int(finite.sum())
-            if keep == B:
-                z_stats.update(per_t_maps)
-            elif keep:
-                z_stats.update(per_t_maps[finite].contiguous())
+            counted = per_t_maps if keep == B else per_t_maps[finite].contiguous() if keep else None
+            if counted is not None:
+                z_stats.update(counted)
+                if self._cal_rows is not None:  # --pixel_calibrate_fpr: the very tensor the statistics received stays on the device
+                    self._cal_rows.append(counted)
             return B - keep
         if self._z_tables is None or self._z_tables[0] != list(t_values) or self._z_tables[1].shape != per_t_maps.shape[1:]:
             self._z_tables = self._z_load_tables(t_values, tuple(per_t_maps.shape[3:]))
@@ -663,11 +690,21 @@ class Reconstruct(BaseTrainer):
         if self.pixel_regions:  # (the component counts and the regions per image ride in the same copy)
             components, regions = self._px_regions_batch(z.reshape(B, 2, H * W), H, W)
             parts += [components.reshape(B, -1), regions[:, None]]
+        n_cal = 0
+        if self.px_calibrate:  # (the counts at the calibrated thresholds ride behind everything else in the same copy)
+            cal = self._px_calibrated_batch(z.reshape(B, 2, H * W), H, W, t_values)
+            n_cal = cal.shape[1]
+            parts.append(cal)
+        self._px.pop("mask", None)
+        self._px.pop("labels", None)
         both = torch.cat(parts, dim=1).cpu()
+        cal_host = both[:, both.shape[1] - n_cal:]
+        both = both[:, :both.shape[1] - n_cal]
         zmaps_all.append(both[:, :2 * H * W].contiguous().view(torch.float32).reshape(B, 2, H, W))
         n_counts = counts[0].numel()
         rows = [both[:, 2 * H * W:2 * H * W + n_counts], mask_pixels.to(torch.int32)[:, None], both[:, 2 * H * W + n_counts:]]
-        self._px["rows"].append(torch.cat(rows, dim=1))  # [counts | mask_pixels | with --pixel_regions 1: components | regions]
+        # [counts | mask_pixels | with --pixel_regions 1: components | regions | with --pixel_calibrate_fpr: the calibrated counts]
+        self._px["rows"].append(torch.cat(rows + [cal_host], dim=1))
         return 0
 
     def _px_batch(self, z, mask):
@@ -694,8 +731,8 @@ class Reconstruct(BaseTrainer):
             zc = z[:, c].contiguous()
             ops.map_mask_hist(zc, m, self.px_lo, self.px_hi, self.px_bins, total=self._px["hist"][c])
             counts.append(ops.map_mask_counts(zc, m, self._px_thr))
-        if self.pixel_regions:
-            self._px["mask"] = m  # (for _px_regions_batch)
+        if self.pixel_regions or self.px_calibrate:
+            self._px["mask"] = m  # (for _px_regions_batch / _px_calibrated_batch)
         return torch.stack(counts, dim=1), mask_pixels
 
     def _px_regions_batch(self, z, H, W):
@@ -707,8 +744,9 @@ class Reconstruct(BaseTrainer):
         if P > ops.MAP_LABEL_MAX_PIXELS:
             raise ValueError(f"--pixel_regions 1: maps of {H} x {W} pixels are above the {ops.MAP_LABEL_MAX_PIXELS} pixels "
                              f"(128 x 128) a labelled plane may have")
-        m = self._px.pop("mask").reshape(B, H, W)
+        m = self._px["mask"].reshape(B, H, W)
         labels, regions = ops.map_label(m, self.px_connectivity)
+        self._px["labels"] = (labels, regions)  # (for _px_calibrated_batch)
         if self._px.get("overlap") is None:
             self._px["overlap"] = torch.zeros((2, self.px_bins + 1), dtype=torch.float64, device=self.device)
         components = []
@@ -717,6 +755,78 @@ class Reconstruct(BaseTrainer):
             ops.map_region_overlap(zc, labels, regions, self.px_lo, self.px_hi, self.px_bins, total=self._px["overlap"][c])
             components.append(ops.map_component_counts(zc, m, labels, regions, self._px_thr, self.px_connectivity))
         return torch.stack(components, dim=1), regions
+
+    def _px_calibrated_batch(self, z, H, W, t_values):
+        """--pixel_calibrate_fpr with --pixel_metrics 1, one batch, after ``_px_batch`` (and ``_px_regions_batch``): per channel one
+        more counts call at that channel's calibrated thresholds, with --pixel_regions 1 one more component-counts call.  Returns
+        int32 [B, 2 F 3] (with regions [B, 2 F 3 + 2 F 3]) on the device: the counts of both channels, then the components."""
+        B = z.shape[0]
+        thr = self._cal_load(t_values)["thr"]
+        m = self._px["mask"]
+        counts = [ops.map_mask_counts(z[:, c].contiguous(), m, thr[c]) for c in range(2)]
+        parts = [torch.stack(counts, dim=1).reshape(B, -1)]
+        if self.pixel_regions:
+            labels, regions = self._px["labels"]
+            comps = [ops.map_component_counts(z[:, c].contiguous().reshape(B, H, W), m.reshape(B, H, W), labels, regions, thr[c],
+                                              self.px_connectivity) for c in range(2)]
+            parts.append(torch.stack(comps, dim=1).reshape(B, -1))
+        return torch.cat(parts, dim=1)
+
+    def _cal_set(self, cal):
+        self._cal = dict(cal, thr=torch.from_numpy(np.ascontiguousarray(cal["thresholds"], dtype=np.float32)).to(self.device))
+        return self._cal
+
+    def _cal_load(self, t_values):
+        """The calibration of this process's validation pass, else that of ood/calibration.npz (--run_val 0), which must have
+        been written with this run's t-starts, range, bins, smoothing, floor and target rates."""
+        if self._cal is None or [int(t) for t in self._cal["t"]] != [int(t) for t in t_values]:
+            if self.last_calibration is not None:
+                raise ValueError(f"--pixel_calibrate_fpr: the validation pass calibrated on t = {[int(t) for t in self.last_calibration['t']]}"
+                                 f", this set has t = {list(t_values)}")
+            self._cal_set(pixel_metrics.load_calibration(self.out_dir / pixel_metrics.CALIBRATION_FILE, t_values, self.px_lo,
+                                                         self.px_hi, self.px_bins, self.z_sigma, self.z_std_floor, self.cal_fprs))
+        return self._cal
+
+    def _cal_finish_validation(self, stats, t_values):
+        """--pixel_calibrate_fpr, after ``_z_finish_validation``: every rank uploads the merged mean and M2 (float64 rounded once to
+        fp32; the same tables on every rank) and the floor, forms the leave-one-out Z-maps of the rows it kept batch by batch
+        (smoothed like every other set's) and bins them per channel; with N ranks ONE all_reduce of the int64 table.  Every rank
+        derives the same thresholds; rank 0 keeps the file's contents for ``_write``."""
+        rows, self._cal_rows = self._cal_rows, None
+        n, mean, m2 = stats.tables()
+        if n < 3:
+            raise ValueError(f"--pixel_calibrate_fpr: leaving one of {n} validation image(s) out leaves fewer than 2: at least 3 are needed")
+        mean_d = torch.from_numpy(mean.astype(np.float32)).to(self.device)
+        m2_d = torch.from_numpy(m2.astype(np.float32)).to(self.device)
+        floor_d = torch.from_numpy(stats.floor(self.z_std_floor)).to(self.device)
+        hist = torch.zeros((2, 2, self.px_bins + 1), dtype=torch.int64, device=self.device)  # [channel, class, bin]: class 1 stays 0
+        kept = []
+        for per_t in rows:
+            B, _, _, H, W = per_t.shape
+            z = ops.map_zscore_loo(per_t, mean_d, m2_d, n, floor_d)
+            if self.z_sigma > 0:
+                if self._z_taps is None:
+                    self._z_taps = torch.from_numpy(ops.gaussian_taps(self.z_sigma).astype(np.float32)).to(self.device)
+                z = ops.map_blur(z.reshape(B * 2, H, W), taps=self._z_taps)
+            z = z.reshape(B, 2, H * W)
+            if self._px_no_mask is None or self._px_no_mask.shape[0] < B or self._px_no_mask.shape[1] != H * W:
+                self._px_no_mask = torch.zeros((B, H * W), dtype=torch.uint8, device=self.device)
+            for c in range(2):
+                ops.map_mask_hist(z[:, c].contiguous(), self._px_no_mask[:B], self.px_lo, self.px_hi, self.px_bins, total=hist[c])
+            if self.keep_calibration_rows:
+                kept.append((per_t.cpu(), z.reshape(B, 2, H, W).cpu()))
+        hist = hist[:, 0].contiguous()
+        if self.ddp:
+            if dist.get_backend() == "gloo" and hist.is_cuda:  # (the test hook of gather_scores)
+                hist = hist.cpu()
+            dist.all_reduce(hist, op=dist.ReduceOp.SUM)
+        if self.keep_calibration_rows:
+            self.calibration_rows = torch.cat([k[0] for k in kept]).numpy() if kept else None
+            self.calibration_zmaps = torch.cat([k[1] for k in kept]).numpy() if kept else None
+        cal = pixel_metrics.calibration_tables(hist.cpu().numpy(), t_values, n, self.cal_fprs, self.px_lo, self.px_hi, self.px_bins,
+                                               self.z_sigma, self.z_std_floor)
+        self.last_calibration = cal
+        self._cal_set(cal)
 
     def _z_set_tables(self, stats, t_values):
         mean, inv_std = stats.finalize(self.z_std_floor)
@@ -830,6 +940,15 @@ class Reconstruct(BaseTrainer):
         if got is not None:
             stems, rows = got
             rows = np.rint(rows).astype(np.int64)
+            if self.px_calibrate:  # the trailing columns: counts [2, F, 3] at the calibrated thresholds, with regions components [2, F, 3]
+                F = len(self.cal_fprs)
+                n_cal = 2 * F * 3 * (2 if self.pixel_regions else 1)
+                rows, cal_rows = rows[:, :-n_cal], rows[:, -n_cal:].astype(np.int32)
+                self.last_calibrated = {"filename": np.asarray(stems), "fpr": np.asarray(self._cal["fpr"], dtype=np.float64),
+                                        "thresholds": np.asarray(self._cal["thresholds"], dtype=np.float32),
+                                        "counts": cal_rows[:, :2 * F * 3].reshape(-1, 2, F, 3)}
+                if self.pixel_regions:
+                    self.last_calibrated["components"] = cal_rows[:, 2 * F * 3:].reshape(-1, 2, F, 3)
             if self.pixel_regions:  # the columns behind mask_pixels: components [2, K, 3], regions
                 rows, extra = rows[:, :2 * K * 3 + 1], rows[:, 2 * K * 3 + 1:]
                 self.last_regions = {"filename": np.asarray(stems), "t": np.asarray(t_values, dtype=np.int64),
@@ -895,7 +1014,15 @@ class Reconstruct(BaseTrainer):
                 # filename [N], t, channels, lo, hi, nbins, connectivity, regions int32 [N], overlap float64 [2, nbins + 1],
                 # thresholds [K], components int32 [N, 2, K, 3] = (hit, pred, false_pred), sigma
                 np.savez(self.out_dir / f"regions_{name}.npz", **self.last_regions)
-        self.last_maps = self.last_zmaps = self.last_pixels = self.last_regions = None
+            if self.px_calibrate and name == "val" and self.last_calibration is not None:
+                # t [n_t], n, fpr [F], bin int64 [2, F], thresholds fp32 [2, F], hist int64 [2, nbins + 1], lo, hi, nbins, sigma,
+                # rel_floor, channels
+                np.savez(self.out_dir / pixel_metrics.CALIBRATION_FILE, **self.last_calibration)
+            if self.px_calibrate and self.last_calibrated is not None:
+                # filename [N], fpr [F], thresholds fp32 [2, F], counts int32 [N, 2, F, 3] = (TP, FP, FN), with --pixel_regions 1
+                # components int32 [N, 2, F, 3] = (hit, pred, false_pred)
+                np.savez(self.out_dir / f"calibrated_{name}.npz", **self.last_calibrated)
+        self.last_maps = self.last_zmaps = self.last_pixels = self.last_regions = self.last_calibrated = None
 
     def reconstruct(self, args):
         if bool(args.run_val):

@@ -35,6 +35,21 @@ def check_flags(spatial_dimension, vqvae_checkpoint, sigma: float = 0.0, rel_flo
         raise ValueError(f"{FLAG}: --anomaly_z_std_floor must lie in (0, 1], got {rel_floor}")
 
 
+def std_floor(std, rel_floor: float):
+    """floor[t, c] = rel_floor * the largest std of that (t, c) over the pixels, float64 [n_t, 2, 1, 1], from the fp32 std table:
+    the absolute floor of the divisor.  ``finalize_tables`` (the in / out sets) and ``MapStats.floor`` (the leave-one-out Z-maps of
+    the validation set) both take it from here."""
+    std = np.asarray(std, dtype=np.float32)
+    if std.ndim != 4:
+        raise ValueError(f"map statistics want a [n_t, 2, H, W] std table, got {std.shape}")
+    top = std.astype(np.float64).max(axis=(2, 3), keepdims=True)
+    if not np.isfinite(top).all() or (top <= 0).any():
+        bad = [(int(t), CHANNELS[int(c)]) for t, c in zip(*np.nonzero(~(top[:, :, 0, 0] > 0) | ~np.isfinite(top[:, :, 0, 0])))]
+        raise ValueError(f"map statistics: no pixel of (t index, channel) {bad} varies over the validation set (largest std 0 or "
+                         f"not finite): nothing to normalise by")
+    return float(rel_floor) * top
+
+
 def finalize_tables(mean, std, rel_floor: float):
     """(mean fp32, inv_std fp32) from the fp32 tables ``map_stats.npz`` holds: inv_std = 1 / max(std, floor[t, c]) with
     floor[t, c] = rel_floor * the largest std of that (t, c) over the pixels, in float64, rounded once.  Both a run's own validation
@@ -42,12 +57,7 @@ def finalize_tables(mean, std, rel_floor: float):
     mean, std = np.asarray(mean, dtype=np.float32), np.asarray(std, dtype=np.float32)
     if mean.shape != std.shape or mean.ndim != 4:
         raise ValueError(f"map statistics want two [n_t, 2, H, W] tables, got {mean.shape} and {std.shape}")
-    top = std.astype(np.float64).max(axis=(2, 3), keepdims=True)
-    if not np.isfinite(top).all() or (top <= 0).any():
-        bad = [(int(t), CHANNELS[int(c)]) for t, c in zip(*np.nonzero(~(top[:, :, 0, 0] > 0) | ~np.isfinite(top[:, :, 0, 0])))]
-        raise ValueError(f"map statistics: no pixel of (t index, channel) {bad} varies over the validation set (largest std 0 or "
-                         f"not finite): nothing to normalise by")
-    inv = 1.0 / np.maximum(std.astype(np.float64), float(rel_floor) * top)
+    inv = 1.0 / np.maximum(std.astype(np.float64), std_floor(std, rel_floor))
     return mean, inv.astype(np.float32)
 
 
@@ -123,6 +133,11 @@ class MapStats:
         """(mean, inv_std) as fp32 [n_t, 2, H, W]: ``finalize_tables`` of the fp32 mean and std."""
         std = self.std()
         return finalize_tables(self.tables()[1].astype(np.float32), std, rel_floor)
+
+    def floor(self, rel_floor: float = 0.01):
+        """The absolute floor of the divisor per (t, channel), fp32 [n_t, 2]: ``std_floor`` of the fp32 std, rounded once -- what
+        ``ops.map_zscore_loo`` takes, and the number ``finalize`` floors the in / out sets' divisor at."""
+        return std_floor(self.std(), rel_floor)[:, :, 0, 0].astype(np.float32)
 
     def save(self, path, t_values, rel_floor: float = 0.01):
         n, mean, _ = self.tables()

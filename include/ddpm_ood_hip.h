@@ -472,6 +472,16 @@ int ddpm_map_stats_update_f32(const float *values, int B, int64_t P, int64_t n_p
  * row's bits depend neither on B nor on its place in the batch; a NaN stays at its own pixel.                             */
 int ddpm_map_zscore_f32(const float *values, const float *mean, const float *inv_std, float *out, int B, int n_t, int64_t P1,
                         float weight, ddpm_stream_t stream);
+/* The Z-map of a row that was itself counted in the statistics, against the OTHER n - 1 rows (leave-one-out).
+ * values: [B, n_t, 2, plane]; mean, m2: [n_t, 2, plane], the full set's mean and sum of squared deviations over its n rows;
+ * floor: [n_t, 2], the absolute floor of the divisor per (t, channel); out: [B, 2, plane].  Per column, t ascending, with
+ * r1 = n / (n - 1) and r2 = 1 / (n - 2) formed in float64 by this entry point and rounded once to fp32:
+ *   d = v - mean;  dl = d * r1;  q = max(m2 - d * dl, 0);  s = sqrt(q * r2);  acc (+)= dl / max(s, floor[t, c]);  out = acc * weight
+ * (the sum starts with its first addend).  16-byte accesses when plane is a multiple of 4 and values, mean, m2 and out are
+ * 16-byte aligned, else the scalar path: the same bits.  A row's bits depend on the row and the tables alone; a NaN value gives
+ * a NaN at its own pixel.  Refused with -1: n < 3, a null pointer, an out that overlaps an input.                          */
+int ddpm_map_zscore_loo_f32(const float *values, const float *mean, const float *m2, const float *floor, float *out, int B,
+                            int n_t, int64_t plane, int64_t n, float weight, ddpm_stream_t stream);
 /* Separable smoothing of [N, H, W] maps with the 2 radius + 1 weights of taps (a device buffer), scipy.ndimage's
  * mode="reflect" boundary:  tmp[y, x] = sum_k taps[k] in[refl(y + k - radius, H), x], then out[y, x] = sum_k taps[k]
  * tmp[y, refl(x + k - radius, W)], k ascending, each sum starting with its first product;  refl(i, L): m = i mod 2L (not

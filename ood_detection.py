@@ -31,6 +31,11 @@ def parse_args(argv=None):
                         "region-overlap score (AUPRO) and, per fixed threshold, region recall, component precision and their F1")
     p.add_argument("--pixel_pro_fpr", type=float, default=0.3,
                    help="--score pixel --pixel_regions 1: the false-positive rate up to which the region-overlap curve is integrated")
+    p.add_argument("--pixel_calibrated", type=int, default=0,
+                   help="--score pixel: 1 also reads calibration.npz and the calibrated_*.npz files of reconstruct.py "
+                        "--pixel_calibrate_fpr and prints, per target rate, the threshold calibrated on the validation set, the rate "
+                        "it reaches there and on the in set (pixels_in.npz), the pooled and the mean per-image Dice and, with "
+                        "--pixel_regions 1, the component scores")
     p.add_argument("--zmap_reduce", default="mean", choices=["mean", "max"], help="--score zmap: mean or maximum over the pixels")
     return p.parse_args(argv)
 

@@ -76,6 +76,13 @@ _EXTENSIONS = [
                               "against the Z-maps: the per-region overlap table (AUPRO) and per-image component counts at the "
                               "fixed thresholds (ood_detection.py --score pixel --pixel_regions 1); planes up to 128 x 128"),
     ("pixel_pro_fpr", float, 0.3, "--pixel_regions 1: the false-positive rate up to which the region-overlap curve is integrated"),
+    ("pixel_calibrate_fpr", str, None, "comma list of 1 .. 8 target false-positive rates in (0, 1), e.g. 0.05,0.01,0.001 (with "
+                                       "--anomaly_z_maps 1): also write ood/calibration.npz, the Z thresholds above which those "
+                                       "fractions of the validation set's leave-one-out Z-map pixels fall (bins of --pixel_range / "
+                                       "--pixel_bins), and with --pixel_metrics 1 ood/calibrated_<name>.npz, the per-image counts "
+                                       "at them (ood_detection.py --score pixel --pixel_calibrated 1); --run_val 0 reads the file"),
+    ("pixel_calibrate_budget_gb", float, 8.0, "--pixel_calibrate_fpr: the most device memory (GiB per rank) the validation set's "
+                                              "per-t maps may take while they wait for the leave-one-out pass"),
 ]
 
 
