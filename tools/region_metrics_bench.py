@@ -155,14 +155,8 @@ def main():
                 m = loaders["out"].masks
                 m = (torch.stack(list(m)) if isinstance(m, list) else m)[:a.batch].reshape(-1, 32, 32).contiguous().to(dev)
                 z = torch.randn(m.shape[0], 2, 32 * 32, device=dev)
-                tr = trainers[1]
-                tr._px = {"hist": None, "rows": []}
-
-                def batch_calls():
-                    tr._px["mask"] = m
-                    tr._px_regions_batch(z, 32, 32)
-
-                us = profiled(lib, batch_calls, launches=20)
+                region_pass = trainers[1].map_pipeline.begin("out", loaders["out"], [])
+                us = profiled(lib, lambda: region_pass.region_step(z, m, 32, 32), launches=20)
                 out["per_batch_us"] = {**us, "sum": round(us["map_label_u8"] + 2 * us["map_region_overlap"] + 2 * us["map_component_counts"], 2)}
             finally:
                 sys.stdout = stdout
