@@ -135,8 +135,11 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 // Pairwise (Chan) merge of per-lane {mean, M2} of `cnt` values each over aligned groups of 4 / 16 / 32 lanes on the VALU's
 // DPP path (no LDS traffic): row_shr:1, 2, 4, 8 then row_bcast:15 -- lane i takes in the finished half to its left, so the
-// group's statistics are valid in its LAST lane only (other lanes end with partial garbage).  Exact to rounding whatever the
-// means are, fixed order -> bit-reproducible.
+// group's statistics are valid in its LAST lane only (other lanes end with partial garbage).  No cancellation of large sums,
+// but not independent of the means either: dl is the difference of two partial means that were each rounded at the scale of
+// the offset, so M2 carries a relative error proportional to kappa = max|x| / sigma -- measured 2.1e-8 kappa (16-value leaves)
+// to 3.5e-8 kappa (4-value leaves) on an MI355X, held to 2e-5 + 1e-7 kappa, the mean to 8 * 2^-24 max|x|
+// (tests/test_gpu_gn_conditioning.py); constant inputs merge exactly (M2 == 0).  Fixed order -> bit-reproducible.
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov0(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
