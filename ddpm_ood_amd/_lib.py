@@ -164,6 +164,9 @@ SIGNATURES = {
     "ddpm_map_region_overlap_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ddpm_map_component_counts_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # ---- predicted segmentations: median filter, size-filtered components (additive: the ABI version stays)
+    "ddpm_map_median_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "ddpm_map_segment_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5),
     "ddpm_lpips_layer_backward_f32":(C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
     "ddpm_maxpool3s2_backward_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_int] * 4 + [C.c_void_p]),
     "ddpm_lpips_conv1_dgrad_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p]),

@@ -1,5 +1,5 @@
 """The anomaly-map stack of ``reconstruct.py``: what ``Reconstruct`` does with a batch's maps once its scores
-are final.  ``MapSettings`` is the five opt-in flags, checked before any device is touched; ``MapPipeline`` holds what outlives a
+are final.  ``MapSettings`` is the six opt-in flags, checked before any device is touched; ``MapPipeline`` holds what outlives a
 pass, ``MapPass`` what one ``get_scores`` call accumulates, and ``RowLayout`` names the columns of the per-image integer row that
 rides behind the Z-map bits in a batch's one device->host copy.  Everything is built lazily: with every flag off nothing is
 allocated, launched, gathered or written.
@@ -18,7 +18,9 @@ import torch.distributed as dist
 from . import ops, pixel_metrics, zmaps
 
 # what ``MapPass.collect`` returns on rank 0: {file name with the set's name left open: the arrays of the .npz, in key order}
-MAPS, ZMAPS, PIXELS, REGIONS, CALIBRATED = (f"{kind}_{{name}}.npz" for kind in ("maps", "zmaps", "pixels", "regions", "calibrated"))
+MAPS, ZMAPS, PIXELS, REGIONS, CALIBRATED, SEGMENTS = (f"{kind}_{{name}}.npz" for kind in ("maps", "zmaps", "pixels", "regions", "calibrated",
+                                                                                         "segments"))
+SEG_BITS = 16  # pixels of a segmentation per fp32 of a row: a sum of 16 distinct powers of two below 2^16 is exact
 
 
 @dataclass(frozen=True)
@@ -40,6 +42,11 @@ class MapSettings:
     cal_fprs: list = None
     cal_budget: int = None
     keep_calibration_rows: bool = False  # test hook (not a CLI flag): see ``MapPipeline.calibration_rows``
+    pixel_segment: bool = False  # segments_<name>.npz: the Z-maps thresholded, median-filtered, small components removed
+    sg_median: int = None
+    sg_min_component: int = None
+    sg_thresholds: list = None
+    sg_connectivity: int = None
 
     @classmethod
     def from_args(cls, args):
@@ -47,7 +54,7 @@ class MapSettings:
         s = dict(anomaly_maps=bool(getattr(args, "anomaly_maps", 0)), anomaly_z_maps=bool(getattr(args, "anomaly_z_maps", 0)),
                  z_sigma=float(getattr(args, "anomaly_z_sigma", 0.0) or 0.0), z_std_floor=float(getattr(args, "anomaly_z_std_floor", 0.01)),
                  pixel_metrics=bool(getattr(args, "pixel_metrics", 0)), pixel_regions=bool(getattr(args, "pixel_regions", 0)),
-                 px_calibrate=bool(getattr(args, "pixel_calibrate_fpr", None)),
+                 px_calibrate=bool(getattr(args, "pixel_calibrate_fpr", None)), pixel_segment=bool(getattr(args, "pixel_segment", 0)),
                  keep_calibration_rows=bool(getattr(args, "keep_calibration_rows", False)))
         if s["anomaly_maps"] and (int(args.spatial_dimension) != 2 or args.vqvae_checkpoint):
             raise ValueError("--anomaly_maps 1: anomaly maps cover 2-D pixel-space models only (no --spatial_dimension 3, no "
@@ -68,6 +75,8 @@ class MapSettings:
                 s["anomaly_z_maps"], args.pixel_calibrate_fpr, getattr(args, "pixel_calibrate_budget_gb", pixel_metrics.DEFAULT_BUDGET_GB))
             if not s["pixel_metrics"]:  # (the bins of the validation histogram are those of --pixel_range / --pixel_bins)
                 s["px_lo"], s["px_hi"], s["px_bins"] = pixel_metrics.check_flags(True, None, None, *bins)[:3]
+        if s["pixel_segment"]:
+            s["sg_median"], s["sg_min_component"], s["sg_thresholds"], s["sg_connectivity"] = pixel_metrics.check_segment_flags(args)
         return cls(**s)
 
 
@@ -138,6 +147,20 @@ def gather_rows(ids: torch.Tensor, rows: torch.Tensor, n_max: int = None, who: s
     return out[:, 0].to(torch.int32), out[:, 1:].reshape((-1,) + trailing), [int(c) for c in counts]
 
 
+def check_plane(flag: str, H: int, W: int):
+    """The labelling holds a plane's 16-bit parents in LDS."""
+    if H * W > ops.MAP_LABEL_MAX_PIXELS:
+        raise ValueError(f"{flag}: maps of {H} x {W} pixels are above the {ops.MAP_LABEL_MAX_PIXELS} pixels "
+                         f"(128 x 128) a labelled plane may have")
+
+
+def unpack_segmentation(packed, shape):
+    """uint8 [n, *shape] from the rows' fp32 [n, ceil(prod(shape) / SEG_BITS)] (numpy), SEG_BITS pixels to a value, lowest bit first."""
+    v = np.rint(packed).astype(np.int64)
+    bits = ((v[:, :, None] >> np.arange(SEG_BITS)) & 1).astype(np.uint8).reshape(v.shape[0], -1)
+    return np.ascontiguousarray(bits[:, :int(np.prod(shape, dtype=np.int64))]).reshape((v.shape[0],) + tuple(shape))
+
+
 def file_stem(filename) -> str:
     """The ``filename`` column of the CSV (reconstruct.py:192-204 of the reference strips .nii / .gz as well)."""
     return Path(filename).stem.replace(".nii", "").replace(".gz", "")
@@ -166,6 +189,10 @@ class MapPipeline:
         # ``keep_calibration_rows``: this rank's retained validation rows [n, n_t, 2, H, W] and their leave-one-out Z-maps, on the host
         self.calibration_rows = self.calibration_zmaps = None
         self._tables = self._taps = self._no_mask = self._cal = None
+        # --pixel_segment 1: T thresholds per channel (the fixed ones, then the calibrated ones); the integer row of an image
+        self.seg_T = (len(s.sg_thresholds) + (len(s.cal_fprs) if s.px_calibrate else 0)) if s.pixel_segment else 0
+        self.seg_layout = RowLayout(0, segments=[("pixels", (2, self.seg_T, 3)), ("components", (2, self.seg_T, 3)),
+                                                 ("removed", (2, self.seg_T, 2)), ("regions", ()), ("mask_pixels", ())]) if s.pixel_segment else None
 
     def begin(self, dataset_name: str, loader, t_values) -> "MapPass":
         return MapPass(self, dataset_name, loader, t_values)
@@ -187,6 +214,14 @@ class MapPipeline:
     @functools.cached_property
     def thresholds(self):
         return torch.tensor(self.s.px_thresholds, dtype=torch.float32, device=self.device)
+
+    @functools.cached_property
+    def seg_thresholds(self):
+        return torch.tensor(self.s.sg_thresholds, dtype=torch.float32, device=self.device)
+
+    @functools.cached_property
+    def seg_bit_weights(self):
+        return torch.tensor([1 << b for b in range(SEG_BITS)], dtype=torch.int32, device=self.device)
 
     def tables(self, t_values, shape, fresh=False):
         """(mean, inv_std) [n_t, 2, H, W] on the device: the statistics of this process's validation pass (``fresh``: it just
@@ -229,6 +264,8 @@ class MapPass:
         self.stats = zmaps.MapStats() if s.anomaly_z_maps and dataset_name == "val" else None
         self.z_maps = s.anomaly_z_maps and dataset_name != "val"  # (the validation set gets no Z-maps)
         self.counting = s.pixel_metrics and dataset_name != "val"
+        self.segmenting = s.pixel_segment and dataset_name != "val"  # (the validation pass does nothing for it)
+        self.seg_rows, self.seg_plane = [], None  # fp32 host rows [B, packed segmentation + integer row], one entry per batch; (H, W)
         self.cal_rows = None  # --pixel_calibrate_fpr, validation: the counted rows' per-t maps, one device tensor per batch
         if s.px_calibrate and self.stats is not None:  # they stay on the device for the leave-one-out pass: refuse first
             shape = tuple(loader.images[0].shape) if len(loader.names) else (0, 0)
@@ -261,6 +298,8 @@ class MapPass:
         mean, inv_std = p.tables(self.t_values, per_t_maps.shape[1:])
         z = ops.map_zscore(per_t_maps.reshape(B, n_t, 2 * H * W), mean.reshape(n_t, 2 * H * W), inv_std.reshape(n_t, 2 * H * W))
         z = p.smooth(z, H, W)
+        if self.segmenting:
+            self.segment_batch(z.reshape(B, 2, H * W), mask if self.counting else None, H, W)
         if not self.counting:
             self.zmaps.append(z.reshape(B, 2, H, W).cpu())
             return
@@ -269,6 +308,49 @@ class MapPass:
         self.zmaps.append(both[:, :2 * H * W].contiguous().view(torch.float32).reshape(B, 2, H, W))
         self.rows.append(p.layout.pack(dict(p.device_layout.unpack(both[:, 2 * H * W:]), mask_pixels=mask_pixels)))
 
+    def device_mask(self, mask, B: int, P: int, flag: str = "--pixel_metrics 1"):
+        """(uint8 [B, P] on the device, the masks' pixel counts [B] on the host) of a batch's ``mask`` (None: all zero)."""
+        if mask is None:
+            return self.p.zero_mask(B, P), torch.zeros(B, dtype=torch.int64)
+        if mask.shape[0] != B or mask.numel() != B * P:
+            raise ValueError(f"{flag}: masks of {tuple(mask.shape)} for maps of {B} x {P} pixels")
+        return mask.reshape(B, P).to(device=self.p.device, dtype=torch.uint8).contiguous(), (mask.reshape(B, P) != 0).sum(dim=1).cpu()
+
+    def segment_batch(self, z, mask, H: int, W: int):
+        """--pixel_segment 1: ``z`` [B, 2, H W] on the device, the final Z-maps.  One median launch over the 2 B planes (none at
+        --pixel_median 1), one labelling of the mask, per channel one ``map_segment`` call at the fixed thresholds and, with
+        --pixel_calibrate_fpr, one at the channel's calibrated ones.  The segmentations, 16 pixels to an fp32, and the integer row
+        behind them reach the host in ONE copy."""
+        p, s = self.p, self.p.s
+        B, _, P = z.shape
+        check_plane(pixel_metrics.SEGMENT_FLAG, H, W)
+        m, mask_pixels = self.device_mask(mask, B, P, pixel_metrics.SEGMENT_FLAG)
+        m = m.reshape(B, H, W)
+        planes = z.reshape(2 * B, H, W)
+        if s.sg_median > 1:
+            planes = ops.map_median(planes.contiguous(), s.sg_median)
+        planes = planes.reshape(B, 2, H, W)
+        labels, regions = ops.map_label(m, s.sg_connectivity)
+        cal = p.calibration(self.t_values)["thr"] if s.px_calibrate else None
+        per_channel = []
+        for c in range(2):
+            zc = planes[:, c].contiguous()
+            got = [ops.map_segment(zc, m, labels, regions, p.seg_thresholds, s.sg_min_component, s.sg_connectivity)]
+            if cal is not None:
+                got.append(ops.map_segment(zc, m, labels, regions, cal[c].contiguous(), s.sg_min_component, s.sg_connectivity))
+            per_channel.append([torch.cat(kind, dim=1) for kind in zip(*got)])  # (seg, pixels, components, removed), each [B, T, ...]
+        seg, pixels, components, removed = (torch.stack(kind, dim=1) for kind in zip(*per_channel))  # [B, 2, T, ...]
+        bits = seg.reshape(B, -1)
+        pad = -bits.shape[1] % SEG_BITS
+        if pad:
+            bits = torch.nn.functional.pad(bits, (0, pad))
+        packed = (bits.reshape(B, -1, SEG_BITS).to(torch.int32) * p.seg_bit_weights).sum(dim=2)
+        device_layout = p.seg_layout.without("mask_pixels")
+        ints = device_layout.pack({"pixels": pixels, "components": components, "removed": removed, "regions": regions[:, None]})
+        row = torch.cat([packed, ints], dim=1).to(torch.float32).cpu()  # (every entry is an integer below 2^24: exact)
+        self.seg_plane = (H, W)
+        self.seg_rows.append(torch.cat([row, mask_pixels.to(torch.float32)[:, None]], dim=1))
+
     def count_batch(self, z, mask, H: int, W: int):
         """--pixel_metrics 1: ``z`` [B, 2, H W] on the device against ``mask``; the pixel, region and calibrated steps in the order
         the tables are pinned to.  Returns (the device's columns of the row by name, the masks' pixel counts [B] on the host)."""
@@ -276,13 +358,7 @@ class MapPass:
         B, _, P = z.shape
         if P >= 1 << 31:
             raise ValueError(f"--pixel_metrics 1: maps of {P} pixels do not fit the 32-bit counts")
-        if mask is None:
-            m, mask_pixels = self.p.zero_mask(B, P), torch.zeros(B, dtype=torch.int64)
-        else:
-            if mask.shape[0] != B or mask.numel() != B * P:
-                raise ValueError(f"--pixel_metrics 1: masks of {tuple(mask.shape)} for maps of {B} x {P} pixels")
-            mask_pixels = (mask.reshape(B, P) != 0).sum(dim=1).cpu()
-            m = mask.reshape(B, P).to(device=self.p.device, dtype=torch.uint8).contiguous()
+        m, mask_pixels = self.device_mask(mask, B, P)
         if self.hist is None:
             self.hist = torch.zeros((2, 2, s.px_bins + 1), dtype=torch.int64, device=self.p.device)
         counts = []
@@ -302,9 +378,7 @@ class MapPass:
         table and one component-counts call.  Returns (components int32 [B, 2, K, 3], labels, regions int32 [B]); an all-zero mask: 0."""
         s = self.p.s
         B, _, P = z.shape
-        if P > ops.MAP_LABEL_MAX_PIXELS:
-            raise ValueError(f"--pixel_regions 1: maps of {H} x {W} pixels are above the {ops.MAP_LABEL_MAX_PIXELS} pixels "
-                             f"(128 x 128) a labelled plane may have")
+        check_plane("--pixel_regions 1", H, W)
         m = m.reshape(B, H, W)
         labels, regions = ops.map_label(m, s.px_connectivity)
         if self.overlap is None:
@@ -412,6 +486,8 @@ class MapPass:
                 files[ZMAPS] = {"filename": np.asarray(got[0]), "t": t, "z_lpips_map": np.ascontiguousarray(got[1][:, 0]),
                                 "z_mse_map": np.ascontiguousarray(got[1][:, 1]), "sigma": np.float64(s.z_sigma),
                                 "rel_floor": np.float64(s.z_std_floor)}
+        if self.segmenting:
+            self._collect_segments(files, t, results, *ids)
         if not self.counting:
             return files
         # --pixel_metrics 1: the histogram (and the overlap table) summed over the ranks, ONE all_reduce each, and every rank's integer
@@ -448,6 +524,30 @@ class MapPass:
         files[PIXELS] = {**head, "hist": hist.cpu().numpy().astype(np.int64), "thresholds": thresholds,
                          "counts": row["counts"].astype(np.int32), "mask_pixels": row["mask_pixels"], "sigma": np.float64(s.z_sigma)}
         return files
+
+    def _collect_segments(self, files, t, results, *ids):
+        """--pixel_segment 1: ONE gather of the rows (packed segmentation, integers); the file is saved compressed."""
+        p, s = self.p, self.p.s
+        got = self._gather(pixel_metrics.SEGMENT_FLAG, self.seg_rows, results, *ids)
+        if got is None:
+            return
+        H, W = self.seg_plane
+        T, K = p.seg_T, len(s.sg_thresholds)
+        words = -(-2 * T * H * W // SEG_BITS)
+        row = p.seg_layout.unpack(np.rint(got[1][:, words:]).astype(np.int64))
+        thresholds = np.repeat(np.asarray(s.sg_thresholds, dtype=np.float32)[None], 2, axis=0)
+        fpr = np.full(K, np.nan, dtype=np.float64)
+        if s.px_calibrate:
+            cal = p.calibration(self.t_values)
+            thresholds = np.concatenate([thresholds, np.asarray(cal["thresholds"], dtype=np.float32)], axis=1)
+            fpr = np.concatenate([fpr, np.asarray(cal["fpr"], dtype=np.float64)])
+        arrays = {"filename": np.asarray(got[0]), "t": t, "channels": np.asarray(zmaps.CHANNELS), "thresholds": thresholds, "fpr": fpr,
+                  "median": np.int64(s.sg_median), "min_component": np.int64(s.sg_min_component),
+                  "connectivity": np.int64(s.sg_connectivity), "sigma": np.float64(s.z_sigma),
+                  "segmentation": unpack_segmentation(got[1][:, :words], (2, T, H, W)), "pixels": row["pixels"].astype(np.int32),
+                  "components": row["components"].astype(np.int32), "removed": row["removed"].astype(np.int32),
+                  "mask_pixels": row["mask_pixels"], "regions": row["regions"].astype(np.int32)}
+        files[SEGMENTS] = lambda path, arrays=arrays: np.savez_compressed(path, **arrays)
 
     def _gather(self, flag, batches, results, local_ids, gathered_ids, name_of):
         """(filenames, rows) on rank 0, None elsewhere: every rank's per-image rows (``batches``: this rank's) in the CSV's order."""

@@ -248,10 +248,66 @@ def score_pixels_calibrated(out_dir, out_name, key: str = "z_mse_map", regions: 
     return rows
 
 
+def score_segments(out_npz, in_npz=None, key: str = "z_mse_map"):
+    """The predicted segmentations of one out set (segments_<name>.npz of ``reconstruct.py --pixel_segment 1``) for the
+    Z-map ``key``: a list, one dict per threshold, of ``threshold``, ``fpr`` (the target rate of a calibrated threshold, NaN for a
+    fixed one), ``mean_dice`` (the mean per-image Dice), ``pooled_dice`` (of the summed TP, FP, FN), ``region_recall``,
+    ``component_precision``, ``component_f1`` (``pixel_metrics.component_scores``), ``removed_components`` and ``removed_pixels``
+    (what the size filter dropped, summed over the images).  ``in_npz`` given: also ``in_fpr``, the predicted pixels of the in
+    set's segmentations over all its pixels.  A path or the loaded mapping each."""
+    from . import pixel_metrics as pm
+
+    if key not in pm.KEYS:
+        raise ValueError(f"score_segments: key must be one of {pm.KEYS}, got {key!r}")
+    c = pm.KEYS.index(key)
+    z = np.load(out_npz) if isinstance(out_npz, (str, Path)) else out_npz
+    pixels, components, removed = (np.asarray(z[k])[:, c].astype(np.int64) for k in ("pixels", "components", "removed"))
+    if pixels.ndim != 3 or pixels.shape[2] != 3 or components.shape != pixels.shape or removed.shape != pixels.shape[:2] + (2,):
+        raise ValueError(f"score_segments: pixels / components [N, 2, T, 3] and removed [N, 2, T, 2] expected, got "
+                         f"{np.asarray(z['pixels']).shape}, {np.asarray(z['components']).shape} and {np.asarray(z['removed']).shape}")
+    thresholds, fpr = np.asarray(z["thresholds"])[c], np.asarray(z["fpr"], dtype=np.float64)
+    mean_dice = pm.dice_from_counts(pixels).mean(axis=0)
+    pooled_dice = pm.dice_from_counts(pixels.sum(axis=0))
+    comp = pm.component_scores(components, np.asarray(z["regions"]))
+    in_fpr = None
+    if in_npz is not None:
+        zi = np.load(in_npz) if isinstance(in_npz, (str, Path)) else in_npz
+        if not np.array_equal(np.asarray(zi["thresholds"]), np.asarray(z["thresholds"])) \
+                or any(int(zi[k]) != int(z[k]) for k in ("median", "min_component", "connectivity")):
+            raise ValueError("score_segments: the in set was segmented at other thresholds or with another filter")
+        seg = np.asarray(zi["segmentation"])[:, c]
+        in_fpr = np.asarray(zi["pixels"])[:, c, :, 1].astype(np.float64).sum(axis=0) / float(seg.shape[0] * seg.shape[2] * seg.shape[3])
+    rows = []
+    for j in range(pixels.shape[1]):
+        row = {"threshold": float(thresholds[j]), "fpr": float(fpr[j]), "mean_dice": float(mean_dice[j]), "pooled_dice": float(pooled_dice[j]),
+               **{name: float(comp[name][j]) for name in ("region_recall", "component_precision", "component_f1")},
+               "removed_components": int(removed[:, j, 0].sum()), "removed_pixels": int(removed[:, j, 1].sum())}
+        if in_fpr is not None:
+            row["in_fpr"] = float(in_fpr[j])
+        rows.append(row)
+    return rows
+
+
+def print_segments(model, o, out_dir, key):
+    """``--pixel_segmented 1``: one line per threshold of ``score_segments`` for the out set ``o``."""
+    from . import pixel_metrics as pm
+
+    out = _need(out_dir / f"segments_{o}.npz", pm.SEGMENT_FLAG)
+    rows = score_segments(out, _need(out_dir / "segments_in.npz", pm.SEGMENT_FLAG), key)
+    print(f"Segmentations for {model} vs {o}: median {int(out['median'])}, components below {int(out['min_component'])} pixels removed "
+          f"(connectivity {int(out['connectivity'])})")
+    for r in rows:
+        at = f"Z > {r['threshold']:.4g}" + ("" if np.isnan(r["fpr"]) else f" (validation FPR <= {r['fpr']:g})")
+        print(f"Segmented for {model} vs {o} at {at}: mean image Dice {r['mean_dice']:.4f}, pooled Dice {r['pooled_dice']:.4f}, "
+              f"recall {r['region_recall']:.4f}, component precision {r['component_precision']:.4f}, F1 {r['component_f1']:.4f}, "
+              f"in-set FPR {r['in_fpr']:.5f}, removed {r['removed_components']} components / {r['removed_pixels']} pixels")
+    return rows
+
+
 def main_pixels(args, out_data=None):
     """``ood_detection.py --score pixel``: per out set the pixel AUROC, AP, best Dice and the mean per-image Dice at the fixed
     thresholds, from pixels_<name>.npz (and pixels_in.npz with --pixel_include_in 1).  --pixel_calibrated 1: also the operating
-    points of ``score_pixels_calibrated``."""
+    points of ``score_pixels_calibrated``.  --pixel_segmented 1: also the lines of ``print_segments``."""
     model = args.model_name
     run_dir = Path(args.output_dir) / model
     print(f"Run directory: {str(run_dir)}")
@@ -278,6 +334,8 @@ def main_pixels(args, out_data=None):
             for t in s["region_recall"]:
                 print(f"Regions for {model} vs {o} at Z > {t:g}: recall {s['region_recall'][t]:.4f}, component precision "
                       f"{s['component_precision'][t]:.4f}, F1 {s['component_f1'][t]:.4f}")
+        if bool(getattr(args, "pixel_segmented", 0)):
+            s["segmented"] = print_segments(model, o, out_dir, key)
         if bool(getattr(args, "pixel_calibrated", 0)):
             s["calibrated"] = score_pixels_calibrated(out_dir, o, key, regions)
             for r in s["calibrated"]:

@@ -1086,6 +1086,70 @@ def map_component_counts(maps, masks, labels, regions, thresholds, connectivity:
     return counts
 
 
+# ---- predicted segmentations: median filter, size-filtered components -------------------------------
+
+MAP_MEDIAN_SIZES = (3, 5)
+
+
+def map_median(maps, size: int, out=None):
+    """The ``size`` x ``size`` median (3 or 5, else ValueError) of [N, H, W] fp32 maps, any H, W >= 1:
+    ``scipy.ndimage.median_filter(maps[n], size=size, mode="reflect")`` for NaN-free input; with NaN, element (size^2 - 1) / 2 of
+    ``np.sort`` of the window (a NaN above +inf).  The output is an input value (the sign of a zero among equal zeros and a NaN's
+    payload are not pinned).  ``out``: a contiguous fp32 [N, H, W] to write into; it may not overlap ``maps`` (not in place)."""
+    lib = _lib.load()
+    maps = require_device_f32(maps, "maps")
+    if maps.ndim != 3 or min(maps.shape) < 1:
+        raise ValueError(f"map_median wants [N, H, W] maps, got {tuple(maps.shape)}")
+    if isinstance(size, bool) or size not in MAP_MEDIAN_SIZES:
+        raise ValueError(f"map_median: size must be 3 or 5, got {size!r}")
+    N, H, W = maps.shape
+    out = _fresh_out(out, (N, H, W), maps.device, "map_median")
+    check(lib.ddpm_map_median_f32(ptr(maps), ptr(out), int(size), N, H, W, stream_ptr()), "map_median")
+    return out
+
+
+def map_segment(maps, masks, labels, regions, thresholds, min_size: int, connectivity: int = 8):
+    """Per image and threshold the predicted segmentation ``v > threshold`` with its connected components of fewer than
+    ``min_size`` pixels (1 .. 16 384) removed.  ``maps`` fp32 and ``masks`` uint8 [N, H, W], H W <= 16 384; ``labels`` / ``regions``
+    as ``map_label(masks)`` returns them; ``thresholds``: 1 .. 8 values, a sequence or an fp32 device tensor [K].  Returns, on the
+    device, (seg uint8 [N, K, H, W]: 1 on the kept components; pixels int32 [N, K, 3]: TP, FP, FN of seg against ``mask != 0``;
+    components int32 [N, K, 3]: regions with a kept pixel, kept components, kept components without a masked pixel; removed int32
+    [N, K, 2]: the components and pixels dropped).  At ``min_size`` 1: ``map_mask_counts`` and ``map_component_counts``."""
+    lib = _lib.load()
+    what = "map_segment"
+    connectivity = _connectivity(connectivity, what)
+    N, H, W = _planes(maps, torch.float32, "maps", what)
+    if _planes(masks, torch.uint8, "masks", what) != (N, H, W) or masks.device != maps.device:
+        raise ValueError(f"{what} wants maps and masks of one shape [N, H, W] on one device, got {tuple(maps.shape)} and "
+                         f"{tuple(masks.shape)}")
+    _labels_and_regions(labels, regions, maps.shape, maps.device, what)
+    try:
+        whole = not isinstance(min_size, bool) and int(min_size) == min_size and 1 <= int(min_size) <= MAP_LABEL_MAX_PIXELS
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise ValueError(f"{what}: min_size must be an integer in 1 .. {MAP_LABEL_MAX_PIXELS}, got {min_size!r}")
+    if isinstance(thresholds, torch.Tensor):
+        thr = thresholds
+        if not thr.is_cuda or thr.dtype != torch.float32 or thr.ndim != 1 or not thr.is_contiguous() or thr.device != maps.device:
+            raise ValueError(f"{what}: thresholds must be a contiguous float32 [K] tensor on {maps.device}")
+    else:
+        host = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+        thr = torch.empty((len(host),), dtype=torch.float32, device=maps.device)
+        if len(host):
+            thr.copy_(torch.from_numpy(host))
+    K = int(thr.numel())
+    if not 1 <= K <= MAP_COUNTS_MAX_K:
+        raise ValueError(f"{what}: 1 .. {MAP_COUNTS_MAX_K} thresholds, got {K}")
+    seg = torch.empty((N, K, H, W), dtype=torch.uint8, device=maps.device)
+    pixels = torch.empty((N, K, 3), dtype=torch.int32, device=maps.device)
+    components = torch.empty((N, K, 3), dtype=torch.int32, device=maps.device)
+    removed = torch.empty((N, K, 2), dtype=torch.int32, device=maps.device)
+    check(lib.ddpm_map_segment_f32(ptr(maps), ptr(masks), ptr(labels), ptr(regions), N, H, W, ptr(thr), K, int(min_size), connectivity,
+                                   ptr(seg), ptr(pixels), ptr(components), ptr(removed), stream_ptr()), what)
+    return seg, pixels, components, removed
+
+
 # ---- LPIPS-AlexNet pieces (src/losses/perceptual_loss.py:105-186) -------------------------------------
 
 def lpips_conv(x, weight, bias, stride: int, pad: int, relu: bool = True, in_scale=None, in_shift=None):

@@ -381,3 +381,38 @@ def summarize(hist, lo: float, hi: float, counts=None, thresholds=None):
     if counts is not None:
         out["mean_dice"] = dict(zip([float(t) for t in thresholds], dice_from_counts(counts).mean(axis=0).tolist()))
     return out
+
+
+# ---- predicted segmentations (``--pixel_segment 1``) --------------------------------------------------
+# The device side (``ops.map_median`` / ``map_segment``) leaves per image, channel and threshold the binary segmentation after
+# the median filter and the removal of components below a minimum size, its (TP, FP, FN), (hit, pred, false_pred) and what the
+# size filter dropped (components, pixels).
+
+SEGMENT_FLAG = "--pixel_segment 1"
+DEFAULT_MEDIAN, DEFAULT_MIN_COMPONENT = 3, 4
+MEDIAN_SIZES = (1, 3, 5)
+
+
+def check_segment_flags(args):
+    """What ``Reconstruct`` refuses at construction when ``--pixel_segment 1`` is given, from the Namespace alone (no device needed).
+    Returns (median, min_component, thresholds, connectivity)."""
+    if not bool(getattr(args, "anomaly_z_maps", 0)):
+        raise ValueError(f"{SEGMENT_FLAG} thresholds the Z-maps: it needs --anomaly_z_maps 1 (the raw maps have no fixed scale)")
+    median, small = getattr(args, "pixel_median", DEFAULT_MEDIAN), getattr(args, "pixel_min_component", DEFAULT_MIN_COMPONENT)
+    try:
+        m, n = int(median), int(small)
+        if m != float(median) or n != float(small):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{SEGMENT_FLAG}: --pixel_median and --pixel_min_component are integers, got {median!r} and {small!r}") from None
+    if m not in MEDIAN_SIZES:
+        raise ValueError(f"{SEGMENT_FLAG}: --pixel_median must be 1 (no filter), 3 or 5, got {median}")
+    if not 1 <= n <= MAX_REGION_PIXELS:
+        raise ValueError(f"{SEGMENT_FLAG}: --pixel_min_component must lie in 1 .. {MAX_REGION_PIXELS}, got {small}")
+    thr = parse_thresholds(getattr(args, "pixel_thresholds", None) or DEFAULT_THRESHOLDS)
+    if not 1 <= len(thr) <= MAX_THRESHOLDS or not all(np.isfinite(thr)):
+        raise ValueError(f"{SEGMENT_FLAG}: --pixel_thresholds takes 1 .. {MAX_THRESHOLDS} finite numbers, got {thr}")
+    conn = getattr(args, "pixel_connectivity", DEFAULT_CONNECTIVITY)
+    if conn not in (4, 8):
+        raise ValueError(f"{SEGMENT_FLAG}: --pixel_connectivity must be 4 or 8, got {conn}")
+    return m, n, thr, int(conn)

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .data import get_data_loader
-from .map_passes import (CALIBRATED, MAPS, PIXELS, REGIONS, ZMAPS, MapPipeline, MapSettings, file_stem, gather_rows,  # noqa: F401
+from .map_passes import (CALIBRATED, MAPS, PIXELS, REGIONS, SEGMENTS, ZMAPS, MapPipeline, MapSettings, file_stem, gather_rows,  # noqa: F401
                          map_rows_in_csv_order)
 from .perceptual import PerceptualLoss
 from .scheduler import DDPMScheduler, PNDMScheduler
@@ -573,7 +573,8 @@ class Reconstruct(BaseTrainer):
 
 # read-only views for tests, tools and benchmarks: the files of the last get_scores call until _write forgets them (rank 0; None
 # without the flag), and what the map pipeline keeps across passes
-for _attr, _file in (("last_maps", MAPS), ("last_zmaps", ZMAPS), ("last_pixels", PIXELS), ("last_regions", REGIONS), ("last_calibrated", CALIBRATED)):
+for _attr, _file in (("last_maps", MAPS), ("last_zmaps", ZMAPS), ("last_pixels", PIXELS), ("last_regions", REGIONS), ("last_calibrated", CALIBRATED),
+                     ("last_segments", SEGMENTS)):
     setattr(Reconstruct, _attr, property(lambda self, _file=_file: self._files.get(_file)))
 for _attr in ("last_map_stats", "last_calibration", "calibration_rows", "calibration_zmaps"):
     setattr(Reconstruct, _attr, property(lambda self, _attr=_attr: getattr(self.map_pipeline, _attr)))

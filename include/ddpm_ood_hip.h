@@ -544,6 +544,30 @@ int ddpm_map_component_counts_f32(const float *maps, const uint8_t *masks, const
                                   ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Predicted segmentations from the maps: median filter, size-filtered components (--pixel_segment 1).  Entry
+ * points added without an ABI bump; no size function (the caller allocates every buffer); every pointer but the stream is a
+ * device buffer.  No global atomics, every output element written, no buffer's previous contents read.
+ * ---------------------------------------------------------------------------------- */
+/* out[n, y, x] = element (size^2 - 1) / 2 of the ascending sort of the size^2 values of maps in the window centred at (y, x);
+ * size 3 or 5; maps, out: [N, H, W] fp32, any H, W >= 1.  The plane is extended as scipy.ndimage does with mode="reflect" (the
+ * edge pixel repeated: -1 -> 0, -2 -> 1, H -> H - 1; the reflection repeats when the radius exceeds the plane); the order is
+ * np.sort's: -inf < finite < +inf < NaN (a NaN of either sign).  The output is the selected input value: exact, but the sign of
+ * a zero among equal zeros and the payload of a NaN are not pinned.  Not in place: out may not overlap maps (refused).       */
+int ddpm_map_median_f32(const float *maps, float *out, int size, int N, int H, int W, ddpm_stream_t stream);
+/* Per image n and threshold k (thresholds: [K] fp32, 1 <= K <= 8): the connected components of {v > thr[k]} (a NaN pixel or a
+ * NaN threshold: outside; connectivity 4 or 8) with at least min_size pixels (1 .. 16 384) are KEPT.  maps fp32 / masks uint8
+ * [N, H, W], H * W <= 16 384; labels / regions as ddpm_map_label_u8 leaves them for the masks.
+ *   seg [N, K, H, W] uint8     1 on the pixels of kept components, 0 elsewhere
+ *   pixels [N, K, 3] int32     TP, FP, FN of seg against mask != 0
+ *   components [N, K, 3]       hit (regions with a kept pixel), pred (kept components), false_pred (kept, no masked pixel)
+ *   removed [N, K, 2]          the components and the pixels the size filter dropped
+ * At min_size = 1: ddpm_map_mask_counts_f32, ddpm_map_component_counts_f32, removed = 0, seg = (v > thr).  One workgroup per
+ * (image, threshold); should a bound of the labelling run out (it cannot), that pair's integers are -1.                      */
+int ddpm_map_segment_f32(const float *maps, const uint8_t *masks, const int32_t *labels, const int32_t *regions, int N, int H,
+                         int W, const float *thresholds, int K, int min_size, int connectivity, uint8_t *seg, int32_t *pixels,
+                         int32_t *components, int32_t *removed, ddpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Loss terms of VQ-VAE training (src/trainers/vqvae_trainer.py: 0.001 x PerceptualLoss + JukeboxLoss in the generator loss;
  * SURVEY.md A.8).  Entry points added without an ABI bump.  Everything is deterministic (fixed-order sums, no atomics).
  * ---------------------------------------------------------------------------------- */

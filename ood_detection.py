@@ -36,6 +36,10 @@ def parse_args(argv=None):
                         "--pixel_calibrate_fpr and prints, per target rate, the threshold calibrated on the validation set, the rate "
                         "it reaches there and on the in set (pixels_in.npz), the pooled and the mean per-image Dice and, with "
                         "--pixel_regions 1, the component scores")
+    p.add_argument("--pixel_segmented", type=int, default=0,
+                   help="--score pixel: 1 also reads the segments_*.npz files of reconstruct.py --pixel_segment 1 (the out set's and "
+                        "segments_in.npz) and prints, per threshold, the Dice, the component scores and the in-set false-positive "
+                        "rate of the post-processed segmentations and what the size filter removed")
     p.add_argument("--zmap_reduce", default="mean", choices=["mean", "max"], help="--score zmap: mean or maximum over the pixels")
     return p.parse_args(argv)
 

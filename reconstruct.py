@@ -83,6 +83,13 @@ _EXTENSIONS = [
                                        "at them (ood_detection.py --score pixel --pixel_calibrated 1); --run_val 0 reads the file"),
     ("pixel_calibrate_budget_gb", float, 8.0, "--pixel_calibrate_fpr: the most device memory (GiB per rank) the validation set's "
                                               "per-t maps may take while they wait for the leave-one-out pass"),
+    ("pixel_segment", int, 0, "1 (with --anomaly_z_maps 1): also write ood/segments_<name>.npz, a predicted segmentation per image, "
+                              "channel and threshold (--pixel_thresholds, then those of --pixel_calibrate_fpr): the Z-map median-"
+                              "filtered, thresholded, its components below a minimum size removed (--pixel_connectivity), with its "
+                              "pixel and component counts against the masks if there are any (ood_detection.py --score pixel "
+                              "--pixel_segmented 1); planes up to 128 x 128"),
+    ("pixel_median", int, 3, "--pixel_segment 1: the side of the median filter, 1 (none), 3 or 5"),
+    ("pixel_min_component", int, 4, "--pixel_segment 1: predicted components of fewer pixels are removed (1 .. 16384; 1: none)"),
 ]
 
 
