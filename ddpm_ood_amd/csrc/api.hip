@@ -28,6 +28,11 @@ static int env_int(const char *name, int dflt) {
   const char *v = getenv(name);
   return v && *v ? atoi(v) : dflt;
 }
+static long env_long(const char *name, long dflt) {
+  const char *v = getenv(name);
+  return v && *v ? atol(v) : dflt;
+}
+static bool env_set(const char *name) { return getenv(name) != nullptr; }
 static void load_switches() {
   const bool keep = g_sw.split_f16;
   Switches n;
@@ -38,7 +43,6 @@ static void load_switches() {
   n.w44h_xitem = env_int("DDPM_W44H_XITEM", 1);
   n.w44r_serp = env_int("DDPM_W44R_SERP", 0);
   n.wino44_xmap = env_int("DDPM_WINO44_XMAP", -1);
-  n.w44_abl = env_int("DDPM_W44_ABL", 0);
   n.up_wino44h = env_int("DDPM_UP_WINO44H", 1) != 0;
   n.down_s2h = env_int("DDPM_DOWN_S2H", 1);
   n.conv1x1_f16x3 = env_int("DDPM_CONV1X1_F16X3", 1) != 0;
@@ -55,9 +59,21 @@ static void load_switches() {
   n.attn_waves8 = env_int("DDPM_ATTN_WAVES", 8) != 4;
   n.convin_fast = env_int("DDPM_CONVIN_FAST", 1) != 0;
   n.convout_wave = env_int("DDPM_CONVOUT_WAVE", 1) != 0;
-  n.convout_w16_maxwg = getenv("DDPM_CONVOUT_W16_MAXWG") ? atol(getenv("DDPM_CONVOUT_W16_MAXWG")) : -1;
-  n.convin_blocks_per_cu = getenv("DDPM_CONVIN_BLOCKS_PER_CU") ? atol(getenv("DDPM_CONVIN_BLOCKS_PER_CU")) : 8;
-  n.prof_shapes = getenv("DDPM_PROF_SHAPES") != nullptr;
+  n.convout_w16_maxwg = env_long("DDPM_CONVOUT_W16_MAXWG", -1);
+  n.convin_blocks_per_cu = env_long("DDPM_CONVIN_BLOCKS_PER_CU", 8);
+  n.gn_fwd_reg = env_int("DDPM_GN_FWD_REG", 1) != 0;
+  n.gn_bwd_reg = env_int("DDPM_GN_BWD_REG", 1) != 0;
+  n.gemm_v4 = env_int("DDPM_GEMM_V4", 1) != 0;
+  n.gemm_f16x3 = env_int("DDPM_GEMM_F16X3", 1) != 0;
+  n.wgrad_staged = env_int("DDPM_WGRAD_STAGED", 1) != 0;
+  n.wgrad_waves8 = env_int("DDPM_WGRAD_WAVES", 8) != 4;
+  n.gn_wave = env_int("DDPM_GN_WAVE", 1) != 0;
+  n.conv1x1_dma_min_wg = env_long("DDPM_CONV1X1_DMA_MIN_WG", -1);
+  n.conv1x1_xcd = env_int("DDPM_CONV1X1_XCD", 1) != 0;
+  n.conv1x1_presplit = env_int("DDPM_CONV1X1_PRESPLIT", 1) != 0;
+  n.conv_min_wg128 = env_long("DDPM_CONV_MIN_WG128", 512);
+  n.conv_debug = env_set("DDPM_CONV_DEBUG");
+  n.prof_shapes = env_set("DDPM_PROF_SHAPES");
   n.split_f16 = g_sw_loaded ? keep : true;
   g_sw = n;
   g_sw_loaded = true;

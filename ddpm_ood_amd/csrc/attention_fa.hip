@@ -153,11 +153,11 @@ __device__ __forceinline__ float quad_sum(float v) {
   return a + b;
 }
 
-// PIPE: the scores of block jb + 1 are computed in iteration jb, BEFORE the softmax of block jb -- its serial VALU chain (scale,
+// The scores of block jb + 1 are computed in iteration jb, BEFORE the softmax of block jb -- its serial VALU chain (scale,
 // max, exchange, exp2, split) then has 96 independent MFMAs of the same wave to hide behind instead of stalling both waves of
 // the SIMD in lockstep (every wave passes the block barrier at the same time).  The K ring therefore runs one block ahead of
 // the V ring: iteration jb fetches K(jb + 2) and V(jb + 1).
-template <int NW, bool PIPE>
+template <int NW>
 __global__ __launch_bounds__(64 * NW) void attention_fa_kernel(const f16x8 *__restrict__ planes,
                                                               const float *__restrict__ residual, float *__restrict__ out,
                                                               int C, int N, int heads, float scale_log2e) {
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(64 * NW) void attention_fa_kernel(const f16x8 *__re
     }
   };
   dma_planes(Kp, Kring);
-  if (PIPE && nblk > 1) dma_planes(Kp + kKUnits, Kring + kKUnits);
+  if (nblk > 1) dma_planes(Kp + kKUnits, Kring + kKUnits);
   dma_planes(Vp, Vring);
 
   // q tile of this wave: 8 k-steps x {hi, lo}
@@ -239,11 +239,9 @@ __global__ __launch_bounds__(64 * NW) void attention_fa_kernel(const f16x8 *__re
   };
 
   f32x4 scur[2];
-  if (PIPE) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // K(0) (and K(1), V(0)) have landed
-    scores(Kring, scur);
-  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();  // K(0) (and K(1), V(0)) have landed
+  scores(Kring, scur);
 
   for (int jb = 0; jb < nblk; ++jb) {
     const int stage = jb & 1;
@@ -254,25 +252,17 @@ __global__ __launch_bounds__(64 * NW) void attention_fa_kernel(const f16x8 *__re
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     f32x4 snext[2];
-    if (PIPE) {
-      // K(jb) was read in the previous iteration (or the prologue): its slot takes K(jb + 2); V(jb - 1)'s slot takes V(jb + 1)
+    // K(jb) was read in the previous iteration (or the prologue): its slot takes K(jb + 2); V(jb - 1)'s slot takes V(jb + 1)
 #ifndef FA_NO_DMA  // (static ablations for tools/fa_abl.sh: timing only, wrong results)
-      if (jb + 2 < nblk) dma_planes(Kp + (size_t)(jb + 2) * kKUnits, Kring + stage * kKUnits);
-      if (jb + 1 < nblk) dma_planes(Vp + (size_t)(jb + 1) * kKUnits, Vring + (stage ^ 1) * kKUnits);
+    if (jb + 2 < nblk) dma_planes(Kp + (size_t)(jb + 2) * kKUnits, Kring + stage * kKUnits);
+    if (jb + 1 < nblk) dma_planes(Vp + (size_t)(jb + 1) * kKUnits, Vring + (stage ^ 1) * kKUnits);
 #endif
 #ifndef FA_NO_S
-      if (jb + 1 < nblk) scores(Kring + (stage ^ 1) * kKUnits, snext);
+    if (jb + 1 < nblk) scores(Kring + (stage ^ 1) * kKUnits, snext);
 #else
-      snext[0] = scur[0] * 1.0001f;
-      snext[1] = scur[1] * 0.9999f;
+    snext[0] = scur[0] * 1.0001f;
+    snext[1] = scur[1] * 0.9999f;
 #endif
-    } else {
-      if (jb + 1 < nblk) {
-        dma_planes(Kp + (size_t)(jb + 1) * kKUnits, Kring + (stage ^ 1) * kKUnits);
-        dma_planes(Vp + (size_t)(jb + 1) * kKUnits, Vring + (stage ^ 1) * kKUnits);
-      }
-      scores(Kring + stage * kKUnits, scur);
-    }
     const f16x8 *Vs = Vring + stage * kKUnits;
 
     // ---- online softmax of query c over the block's 32 keys (log2 domain) ----------------------------------------------
@@ -345,10 +335,8 @@ __global__ __launch_bounds__(64 * NW) void attention_fa_kernel(const f16x8 *__re
         __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
       }
     }
-    if (PIPE) {
-      scur[0] = snext[0];
-      scur[1] = snext[1];
-    }
+    scur[0] = snext[0];
+    scur[1] = snext[1];
   }
 
   // ---- normalise, add residual, store [B, C, N] ---------------------------------------------------------------------
@@ -392,20 +380,16 @@ int launch_attention_fa(const float *qkv, const float *residual, float *out, int
     DDPM_CHECK_LAUNCH();
   }
   typedef void (*kern_t)(const f16x8 *, const float *, float *, int, int, int, float);
-  static const kern_t kerns[2][2] = {{attention_fa_kernel<4, false>, attention_fa_kernel<4, true>},
-                                     {attention_fa_kernel<8, false>, attention_fa_kernel<8, true>}};
+  static const kern_t kerns[2] = {attention_fa_kernel<4>, attention_fa_kernel<8>};
   static bool attr_done = false;
   static int cus = 256;
-  static bool pipe = true;
   if (!attr_done) {
-    for (int i = 0; i < 4; ++i)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kerns[i / 2][i % 2]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024);
+    for (int i = 0; i < 2; ++i)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kerns[i]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
       cus = prop.multiProcessorCount;
-    pipe = !(getenv("DDPM_ATTN_FA_PIPE") && atoi(getenv("DDPM_ATTN_FA_PIPE")) == 0);  // A/B: scores one block ahead
     attr_done = true;
   }
   const size_t lds = (size_t)4 * kKUnits * sizeof(f16x8);  // 128 KB: K ring + V ring, two 32 KB slots each
@@ -413,9 +397,9 @@ int launch_attention_fa(const float *qkv, const float *residual, float *out, int
   // 128-query workgroups (eight waves) when that still gives every CU a workgroup, 64-query ones otherwise
   const bool eight = (N % 128) == 0 && (long)B * heads * (N / 128) >= cus;
   if (eight) {
-    hipLaunchKernelGGL(kerns[1][pipe], dim3(N / 128, heads, B), dim3(512), lds, s, planes, residual, out, C, N, heads, sl2);
+    hipLaunchKernelGGL(kerns[1], dim3(N / 128, heads, B), dim3(512), lds, s, planes, residual, out, C, N, heads, sl2);
   } else {
-    hipLaunchKernelGGL(kerns[0][pipe], dim3(N / 64, heads, B), dim3(256), lds, s, planes, residual, out, C, N, heads, sl2);
+    hipLaunchKernelGGL(kerns[0], dim3(N / 64, heads, B), dim3(256), lds, s, planes, residual, out, C, N, heads, sl2);
   }
   DDPM_CHECK_LAUNCH();
   return 0;

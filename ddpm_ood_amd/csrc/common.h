@@ -33,16 +33,15 @@ inline hipStream_t as_stream(ddpm_stream_t s) { return reinterpret_cast<hipStrea
 constexpr int kWave = 64;
 
 // ---- run-time switches (api.hip) ----------------------------------------------------------------
-// The DDPM_* environment switches of DESIGN 4.1 that are looked at per launch, parsed ONCE (ddpm_reload_env() parses them
-// again: the tests flip them inside one process) instead of 3-4 getenv calls per convolution, plus the run-time master
-// switch of the split-f16 kernel families (ddpm_set_split_f16).
+// Every DDPM_* environment switch of DESIGN 4.1 that the library reads: api.hip parses them all on first use, and
+// ddpm_reload_env() parses them all again (the tests and A/B scripts flip them inside one process) -- no other file of the
+// library reads the environment.  Plus the run-time master switch of the split-f16 kernel families (ddpm_set_split_f16).
 struct Switches {
   int conv_wino44 = 1;          // DDPM_CONV_WINO44: 0 no F(4x4) kernels, 2 also for launches smaller than the chip
   bool wino44_f16x3 = true;     // DDPM_WINO44_F16X3
   int wino44_split = 4;         // DDPM_WINO44_SPLIT
   int wino_split = 8;           // DDPM_WINO_SPLIT: most channel-stream splits of a conv_wino.hip launch smaller than half the chip (power of two)
   int wino44_xmap = -1;         // DDPM_WINO44_XMAP (-1: unset, each kernel has its own default)
-  int w44_abl = 0;              // DDPM_W44_ABL
   int w44r_serp = 0;            // DDPM_W44R_SERP: 1 consecutive launches of conv_wino44r.hip walk their items in alternating order (measured: +-0)
   int w44h_xitem = 1;           // DDPM_W44H_XITEM: 0 every item of conv_wino44h.hip refills its pixel ring from scratch (A/B)
   bool up_wino44h = true;       // DDPM_UP_WINO44H
@@ -64,7 +63,19 @@ struct Switches {
   long convout_w16_maxwg = -1;  // DDPM_CONVOUT_W16_MAXWG (-1: two workgroups per CU)
   long convin_blocks_per_cu = 8;  // DDPM_CONVIN_BLOCKS_PER_CU
   bool wgrad_f16x3 = true;      // DDPM_WGRAD_F16X3: 0 the 3x3 weight gradient of the training step stays on the fp32 MFMA
-  bool prof_shapes = false;     // DDPM_PROF_SHAPES
+  bool gn_fwd_reg = true;       // DDPM_GN_FWD_REG: 0 the training GroupNorm forward always as statistics pass + apply pass
+  bool gn_bwd_reg = true;       // DDPM_GN_BWD_REG: 0 never the register-resident GroupNorm backward
+  bool gemm_v4 = true;          // DDPM_GEMM_V4: 0 the training GEMM always on its scalar-load fp32 kernel
+  bool gemm_f16x3 = true;       // DDPM_GEMM_F16X3: 0 the training GEMM never on its split-f16 kernel
+  bool wgrad_staged = true;     // DDPM_WGRAD_STAGED: 0 the first form of the 3x3 weight gradient (4-byte staging loads, no prefetch), the staged form's A/B partner
+  bool wgrad_waves8 = true;     // DDPM_WGRAD_WAVES: 4 never 128 couts (eight waves) per workgroup of the 3x3 weight gradient
+  bool gn_wave = true;          // DDPM_GN_WAVE: 0 never the wave-per-group GroupNorm scale / shift kernel
+  long conv1x1_dma_min_wg = -1; // DDPM_CONV1X1_DMA_MIN_WG: fewest workgroups of a conv1x1_dma.hip launch (-1: per-family default)
+  bool conv1x1_xcd = true;      // DDPM_CONV1X1_XCD: 0 conv1x1_dma.hip's workgroups in plain (pixel tile, cout tile) grid order
+  bool conv1x1_presplit = true; // DDPM_CONV1X1_PRESPLIT: 0 conv1x1_dma.hip splits the weights in registers also when given planes
+  long conv_min_wg128 = 512;    // DDPM_CONV_MIN_WG128: fewest workgroups for which conv_mfma.hip takes 128-pixel tiles
+  bool conv_debug = false;      // DDPM_CONV_DEBUG (set): conv_mfma.hip prints each variant's LDS, registers and occupancy once
+  bool prof_shapes = false;     // DDPM_PROF_SHAPES (set): one profiler row per layer shape
   bool split_f16 = true;        // ddpm_set_split_f16(): false = every split-f16 family runs its fp32-MFMA form
 };
 const Switches &sw();

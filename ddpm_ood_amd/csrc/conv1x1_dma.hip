@@ -80,7 +80,7 @@ bool conv1x1_dma_supported(const ddpm_conv_desc &d) {
   // smaller launches stay with conv_mfma's 64 / 128-pixel tiles and its split-K (DDPM_CONV1X1_DMA_MIN_WG: A/B of the
   // threshold).  Split-f16: half a chip of workgroups already wins (8x8 skip at B = 256, 128 workgroups: 83 -> 55 us;
   // the `big` UNet's q / k / v at B = 16, 192 workgroups: 115 -> 70 us); the f32 loop needed 1.5 waves of the chip
-  static const long min_wg_env = getenv("DDPM_CONV1X1_DMA_MIN_WG") ? atol(getenv("DDPM_CONV1X1_DMA_MIN_WG")) : -1;
+  const long min_wg_env = sw().conv1x1_dma_min_wg;
   const long min_wg = min_wg_env >= 0 ? min_wg_env
                       : conv1x1_f16x3_enabled() ? 64  // (8x8 skip at B = 128, 64 workgroups: 62 -> 50 us)
                                                 : 384;
@@ -354,11 +354,9 @@ int launch_conv1x1_dma(const ddpm_conv_desc &d, hipStream_t s) {
   const int Cin = d.C1 + d.C2;
   ProfScope prof(s, aff ? "conv1x1_dma_gn" : "conv1x1_dma", 2.0 * npix * d.Cout * Cin,
                  4.0 * ((double)npix * Cin + (double)npix * d.Cout * (d.residual ? 2 : 1) + (double)d.Cout * Cin));
-  static const bool xcd_order = !(getenv("DDPM_CONV1X1_XCD") && atoi(getenv("DDPM_CONV1X1_XCD")) == 0);
   const unsigned PT = (unsigned)((npix + kDP - 1) / kDP), CT = d.Cout / kDM;
-  const dim3 grid = xcd_order ? dim3(8 * ((PT + 7) / 8) * CT) : dim3(PT, CT);
-  static const bool pre_on = !(getenv("DDPM_CONV1X1_PRESPLIT") && atoi(getenv("DDPM_CONV1X1_PRESPLIT")) == 0);  // A/B
-  const bool pre = f16x3 && pre_on && d.w_wino44h != nullptr;  // weights pre-split by ddpm_pack_conv1x1_h_weight
+  const dim3 grid = sw().conv1x1_xcd ? dim3(8 * ((PT + 7) / 8) * CT) : dim3(PT, CT);
+  const bool pre = f16x3 && sw().conv1x1_presplit && d.w_wino44h != nullptr;  // weights pre-split by ddpm_pack_conv1x1_h_weight
   if (pre && aff)
     hipLaunchKernelGGL((conv1x1_dma_kernel<true, true, true>), grid, dim3(256), lds, s, d);
   else if (pre)

@@ -153,7 +153,7 @@ static bool pick_geom(const ddpm_conv_desc &d, ConvGeom &g, int ps_cap = 0) {
   const bool ok64 = make_geom(d, 64, g64, ps_cap) && geom_ok(d, g64);
   if (!ok128 && !ok64) return false;
   const long wg128 = ok128 ? (long)g128.ntiles * (d.Cout / kConvNT) : 0;
-  static const long min_wg128 = getenv("DDPM_CONV_MIN_WG128") ? atol(getenv("DDPM_CONV_MIN_WG128")) : 512;
+  const long min_wg128 = sw().conv_min_wg128;
   // prefer 128-pixel tiles when they fill the chip and waste no more MFMA columns than 64-pixel tiles would
   const bool fill128 = ok128 && (!ok64 || (long)g128.TPX * g64.MT >= (long)g64.TPX * g128.MT);
   if (ok128 && ((wg128 >= min_wg128 && fill128) || !ok64)) {
@@ -535,7 +535,7 @@ static int launch_variant(const ddpm_conv_desc &d, const ConvGeom &g_in, hipStre
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma_kernel<NTAPS, NPOS, AFFINE, MT, KG>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
-    if (getenv("DDPM_CONV_DEBUG")) {
+    if (sw().conv_debug) {
       int nb = -1;
       hipFuncAttributes fa{};
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(

@@ -128,7 +128,6 @@ struct W44Geom {
   int UI;           // staging units of 64 pixels per image of an item; a wave pair stages units hv, hv + 2, ...
   int NR;           // staging rounds per wave: ceil(TI * UI / 2), at most 5
   int KT, NIT, IPW, NS, grid;  // as conv_wino.hip: cout tiles, items per (cout tile, part), items per workgroup, slots
-  int abl;          // ablation mask (DDPM_W44_ABL, experiments): 1 no patch transform, 2 no pixel stage, 4 no U DMA
   int xmap;         // 1: an XCD serves ONE cout tile (its L2 keeps that tile's U stream); 0: the cout tiles of a slot share an XCD
   // launches with fewer items than CUs (the 8x8 level at B = 256; small batches): S workgroups share an item, each walks
   // nchunks / S chunks of the channel stream and writes its partial output (after the output transform) into slab
@@ -248,7 +247,6 @@ static bool w44_geom(const ddpm_conv_desc &d, W44Geom &g, bool sizing = false) {
   g.IPW = (int)((items + cus - 1) / cus);
   g.NS = g.parts * ((g.NIT + g.IPW - 1) / g.IPW) * g.S;
   g.grid = g.KT * ((g.NS + 7) / 8) * 8;
-  g.abl = sw().w44_abl;
   g.xmap = (sw().wino44_xmap >= 0 ? sw().wino44_xmap != 0 : 1) && (8 % g.KT == 0);
   if (g.xmap) g.grid = 8 * ((g.NS + 8 / g.KT - 1) / (8 / g.KT));
   return true;
@@ -556,17 +554,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino44_kernel(const ddpm_conv_des
       bv[slot] = lds_b64(va, x * (kC * kT * 4));
     };
     auto slice = [&](int s) {
-#ifdef W44_ABLATION  // timing experiments only
-      if (s < 3 && !(g.abl & 4)) {
-        dma_u(2 * s, nb);
-        if (s < 2) dma_u(2 * s + 1, nb);
-      }
-      if (!(g.abl & 2)) {
-        if (s >= 3 && s < 3 + NR) load_px(std::integral_constant<int, 1 - PAR>{}, s - 3, nL);
-        if (s >= 18 - NR) activate_px(std::integral_constant<int, PAR>{}, s - (18 - NR), pb_a);
-      }
-      if ((s & 1) == 0 && !(g.abl & 1)) tstep(s >> 1, pb_t, nb);
-#else
       if (s < 3) {
         dma_u(2 * s, nb);
         if (s < 2) dma_u(2 * s + 1, nb);
@@ -574,7 +561,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino44_kernel(const ddpm_conv_des
       if (s >= 3 && s < 3 + NR) load_px(std::integral_constant<int, 1 - PAR>{}, s - 3, nL);
       if (s >= 18 - NR) activate_px(std::integral_constant<int, PAR>{}, s - (18 - NR), pb_a);
       if ((s & 1) == 0) tstep(s >> 1, pb_t, nb);
-#endif
     };
     load_pair(0, 0);
     load_pair(1, 1);

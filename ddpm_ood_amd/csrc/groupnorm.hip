@@ -347,9 +347,8 @@ int launch_gn_scale_shift(const float *in1, const float *in2, int C1, int C2, co
   ProfScope prof(s, "gn_scale_shift", 5.0 * B * C * HW, 4.0 * B * C * (double)HW);
   const int cpg = C / groups;
   const long n4 = (HW & 3) == 0 ? (long)cpg * (HW >> 2) : -1;
-  static const bool wave_ok = !(getenv("DDPM_GN_WAVE") && atoi(getenv("DDPM_GN_WAVE")) == 0);
   const int total = B * groups;
-  if (wave_ok && n4 > 0 && cpg <= 64 && n4 <= 64 * 16) {  // a group of <= 4096 floats per wave
+  if (sw().gn_wave && n4 > 0 && cpg <= 64 && n4 <= 64 * 16) {  // a group of <= 4096 floats per wave
     const dim3 grid((total + 3) / 4);
     if (n4 <= 64 * 4)
       hipLaunchKernelGGL(gn_scale_shift_wave_kernel<4>, grid, dim3(256), 0, s, in1, in2, C1, C2, gamma, beta, scale,

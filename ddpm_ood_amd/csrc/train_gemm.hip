@@ -1098,8 +1098,7 @@ extern "C" int ddpm_gemm_f32(const ddpm_gemm_desc *g, ddpm_stream_t stream) {
                  : p.sBk1 == 1 && quad(p.sBn) && kq                                                         ? 1
                  : p.sBn == 1 && quad(p.sBk1) && quad(p.N)                                                  ? 2
                                                                                                             : 0;
-  static const bool plain = getenv("DDPM_GEMM_V4") && atoi(getenv("DDPM_GEMM_V4")) == 0;  // (A/B switch)
-  static const bool no_h = getenv("DDPM_GEMM_F16X3") && atoi(getenv("DDPM_GEMM_F16X3")) == 0;  // (A/B switch)
+  const bool plain = !sw().gemm_v4, no_h = !sw().gemm_f16x3;  // (A/B switches)
   for (int i = 0; i < serial; ++i) {
     if (serial > 1) {
       p.kofs = i * kchunk;
@@ -1126,11 +1125,6 @@ extern "C" int ddpm_gemm_f32(const ddpm_gemm_desc *g, ddpm_stream_t stream) {
 }
 
 namespace {
-// DDPM_WGRAD_STAGED=0: the first form of the kernel (4-byte staging loads, no prefetch) -- the A/B partner of the staged form
-bool wgrad_plain_form() {
-  const char *v = getenv("DDPM_WGRAD_STAGED");
-  return v && atoi(v) == 0;
-}
 bool wgrad_plan(int B, int Cin, int Cout, int Hi, int Wi, int Ho, int Wo, int ksize, int stride, WgradP &p, int Di = 1, int Do = 1) {
   if (ksize != 3 || (stride != 1 && stride != 2) || Cin % kWT || Cout % kWT) return false;
   if (stride == 1 ? (Ho != Hi || Wo != Wi) : (Ho != (Hi + 1) / 2 || Wo != (Wi + 1) / 2)) return false;
@@ -1171,8 +1165,7 @@ bool wgrad_plan(int B, int Cin, int Cout, int Hi, int Wi, int Ho, int Wo, int ks
   if (p.fast && stride == 1 && (Wo == 8 || Wo == 16 || Wo == 32 || Wo == 64) && p.R * Wo == 64) {
     p.h16 = p.NA == (Wo == 8 ? 5 : Wo == 16 ? 6 : Wo == 32 ? 8 : 12) && p.ND == 4 && p.RPI * p.LPR == 64 && p.CPI * p.LPD == 64;
     // 128 couts per workgroup where the staging slots still divide evenly (W >= 16) and the layer has them; DDPM_WGRAD_WAVES=4: A/B
-    static const bool four = getenv("DDPM_WGRAD_WAVES") && atoi(getenv("DDPM_WGRAD_WAVES")) == 4;
-    p.nw = p.h16 && Wo >= 16 && Cout % 128 == 0 && !four && split_f16_on(sw().wgrad_f16x3) && !wgrad_plain_form() ? 8 : 4;
+    p.nw = p.h16 && Wo >= 16 && Cout % 128 == 0 && sw().wgrad_waves8 && split_f16_on(sw().wgrad_f16x3) && sw().wgrad_staged ? 8 : 4;
     const int co = 16 * p.nw;
     p.ACSh = (p.R + 2) * Wo + 8;
     p.DCSh = p.R * (Wo + 8);
@@ -1215,7 +1208,7 @@ void wgrad_attrs() {
 }
 
 // the operand maxima of the split-f16 form into scratch[0 .. 1] (p.part already points behind the head)
-bool wgrad_use_h16(const WgradP &p, bool aligned) { return p.h16 && aligned && split_f16_on(sw().wgrad_f16x3) && !wgrad_plain_form(); }
+bool wgrad_use_h16(const WgradP &p, bool aligned) { return p.h16 && aligned && split_f16_on(sw().wgrad_f16x3) && sw().wgrad_staged; }
 void wgrad_h16_maxima(WgradP &p, float *scratch, hipStream_t s, const unsigned *a_amax = nullptr, int a_n = 0,
                       const unsigned *dy_amax = nullptr, int dy_n = 0) {
   unsigned *mx = reinterpret_cast<unsigned *>(scratch);
@@ -1240,7 +1233,7 @@ void wgrad_h16_maxima(WgradP &p, float *scratch, hipStream_t s, const unsigned *
 void wgrad_launch(const WgradP &p, bool aligned, hipStream_t s) {
   dim3 grid(p.Cout / kWT, p.Cin / kWT, p.S);
   const size_t lds = (size_t)kWT * (p.ACS + p.DCS) * sizeof(float);
-  const bool staged = p.fast && aligned && !wgrad_plain_form();
+  const bool staged = p.fast && aligned && sw().wgrad_staged;
   if (p.amax_d) {
     const size_t ldsh = (size_t)p.LDSh * sizeof(_Float16);
     if (p.nw == 8) {

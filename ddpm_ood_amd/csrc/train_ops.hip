@@ -685,8 +685,7 @@ extern "C" int ddpm_gn_forward_f32(const float *x, const float *gamma, const flo
                      (act == DDPM_ACT_NONE || act == DDPM_ACT_SILU),
                  "gn_forward: bad arguments");
   const int Cg = C / groups;
-  static const bool split = getenv("DDPM_GN_FWD_REG") && atoi(getenv("DDPM_GN_FWD_REG")) == 0;  // (A/B switch)
-  if (!(vec4_ok(HW, {x, y}) && HW <= 1024 && Cg <= 16) || split) {
+  if (!(vec4_ok(HW, {x, y}) && HW <= 1024 && Cg <= 16) || !sw().gn_fwd_reg) {
     int rc = ddpm_gn_stats_f32(x, mean_rstd, B, C, HW, groups, eps, stream);
     if (!rc) rc = ddpm_gn_apply_f32(x, mean_rstd, gamma, beta, y, B, C, HW, groups, act, stream);
     if (!rc && y_absmax) {
@@ -721,8 +720,7 @@ extern "C" int ddpm_gn_backward_f32(const float *x, const float *dy, const float
   // algorithmic traffic: x and dy read, dx written (and read when it accumulates)
   ProfScope prof(s, "train_gn_backward", 0.0, 4.0 * (3 + (accumulate_dx ? 1 : 0)) * B * C * (double)HW);
   const int Cg = C / groups;
-  static const bool two_pass = getenv("DDPM_GN_BWD_REG") && atoi(getenv("DDPM_GN_BWD_REG")) == 0;  // (A/B switch)
-  if (vec4_ok(HW, {x, dy, dx}) && HW <= 1024 && Cg <= 16 && !two_pass) {
+  if (vec4_ok(HW, {x, dy, dx}) && HW <= 1024 && Cg <= 16 && sw().gn_bwd_reg) {
     const int cpw = (Cg + 3) / 4;
     const dim3 grid(B * groups);
 #define DDPM_GN_BWD_REG(CPW, QPL) \

@@ -99,12 +99,16 @@ def test_answers_are_consistent_with_the_selected_row(lib, fix):
                     assert lib.ddpm_conv_kernel_name(C.byref(d)) == b"wino44h", what
 
 
-@pytest.mark.parametrize("var,family", [("DDPM_LINEAR_SKINNY", "linear_skinny"), ("DDPM_CONV_WINOGRAD", "wino"),
-                                        ("DDPM_CONV1X1_DMA", "conv1x1_dma")])
-def test_family_switches_follow_reload_env(lib, fix, monkeypatch, var, family):
+# (the last one: a threshold no launch reaches; a switch that used to be read once into a static)
+_FAMILY_SWITCHES = [("DDPM_LINEAR_SKINNY", "0", "linear_skinny"), ("DDPM_CONV_WINOGRAD", "0", "wino"),
+                    ("DDPM_CONV1X1_DMA", "0", "conv1x1_dma"), ("DDPM_CONV1X1_DMA_MIN_WG", "1000000000", "conv1x1_dma")]
+
+
+@pytest.mark.parametrize("var,value,family", _FAMILY_SWITCHES, ids=[f"{v}-{f}" for v, _, f in _FAMILY_SWITCHES])
+def test_family_switches_follow_reload_env(lib, fix, monkeypatch, var, value, family):
     default = fix["answers"]["default"]
     assert any(a[0] == family for a in default)
-    monkeypatch.setenv(var, "0")  # (conftest: a DDPM_* setenv reloads the switches)
+    monkeypatch.setenv(var, value)  # (conftest: a DDPM_* setenv reloads the switches)
     assert not any(rec.ask(lib, row)[0] == family for row in fix["descs"])
     monkeypatch.delenv(var)
     assert [rec.ask(lib, row) for row in fix["descs"]] == default

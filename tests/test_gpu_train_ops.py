@@ -258,6 +258,46 @@ def test_group_norm_forward_and_backward_vs_autograd(device, B, C, H, act):
     assert rows.shape == (B, C) and _rel(rows, acc.double().cpu().sum(dim=(2, 3))) < 3e-6
 
 
+def test_gn_forward_switch_follows_reload_env(device, monkeypatch):
+    """DDPM_GN_FWD_REG lives in the library's switch table: flipped inside one process it selects the other form at the next launch
+    (it used to be read once into a static).  Which form ran is what the in-library profiler names."""
+    import ctypes
+    import json
+
+    from ddpm_ood_amd import _lib
+    from ddpm_ood_amd import train_ops as T
+
+    B, C, H = 2, 64, 8
+    g = torch.Generator().manual_seed(C + H)
+    x = torch.randn(B, C, H, H, generator=g) * 1.7 + 0.3
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    ref = F.silu(F.group_norm(x.double(), 32, gamma.double(), beta.double(), eps=1e-6))
+    xd, gd, bd = x.to(device), gamma.to(device), beta.to(device)
+    lib = _lib.load()
+
+    def run():
+        buf = ctypes.create_string_buffer(1 << 16)
+        torch.cuda.synchronize()
+        lib.ddpm_prof_report(buf, len(buf))  # (drops whatever an earlier test left unreported)
+        lib.ddpm_prof_enable(1)
+        try:
+            y = T.gn_forward(xd, gd, bd, 32, 1e-6, 1)[0]
+            torch.cuda.synchronize()
+        finally:
+            lib.ddpm_prof_enable(0)
+        n = lib.ddpm_prof_report(buf, len(buf))
+        return y, (set(json.loads(buf.value.decode())) if n > 0 else set())
+
+    y, names = run()
+    assert "train_gn_forward" in names and _rel(y, ref) < 3e-6, (names, _rel(y, ref))
+    monkeypatch.setenv("DDPM_GN_FWD_REG", "0")  # (conftest: a DDPM_* setenv reloads the switches)
+    y, names = run()
+    assert "train_gn_apply" in names and "train_gn_forward" not in names and _rel(y, ref) < 3e-6, (names, _rel(y, ref))
+    monkeypatch.delenv("DDPM_GN_FWD_REG")
+    y, names = run()
+    assert "train_gn_forward" in names and _rel(y, ref) < 3e-6, (names, _rel(y, ref))
+
+
 # ---- the small ones -------------------------------------------------------------------------------------------------------------
 def test_elementwise_and_reduction_kernels(device):
     from ddpm_ood_amd import train_ops as T

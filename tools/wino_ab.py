@@ -1,7 +1,6 @@
 """A/B timing of the Winograd conv layers of the `small` UNet (development tool).
     python tools/wino_ab.py          # F(4x4, 3x3) where it applies (DDPM_CONV_WINO44=0: F(2x2, 3x3) everywhere;
-                                     # DDPM_WINO44_F16X3=0: the fp32-MFMA F(4x4) kernel instead of the split-f16 one)
-    DDPM_WINO_WAVES=4 python tools/wino_ab.py      # the four-wave F(2x2) kernel vs the default eight-wave one"""
+                                     # DDPM_WINO44_F16X3=0: the fp32-MFMA F(4x4) kernel instead of the split-f16 one)"""
 import math
 import os
 import sys
@@ -56,4 +55,4 @@ for B, C1, C2, Cout, H in SHAPES:
     fl = 2.0 * B * H * H * Cout * Cin * 9
     print(f"{C1}+{C2}->{Cout}@{H}: {ms * 1e3:8.1f} us  {fl / ms / 1e9:7.2f} alg TFLOP/s  ({fl / ms / 1e9 * EXECUTED / PEAK:.3f} of {FORM} peak)  "
           f"err vs direct {err:.1e}", flush=True)
-print(f"F16X3={os.environ.get('DDPM_WINO44_F16X3', '1')} WAVES={os.environ.get('DDPM_WINO_WAVES', '8')} WINO44={os.environ.get('DDPM_CONV_WINO44', '1')} SPLIT44={os.environ.get('DDPM_WINO44_SPLIT', '4')} total {tot * 1e3:.1f} us", flush=True)
+print(f"F16X3={os.environ.get('DDPM_WINO44_F16X3', '1')} WINO44={os.environ.get('DDPM_CONV_WINO44', '1')} SPLIT44={os.environ.get('DDPM_WINO44_SPLIT', '4')} total {tot * 1e3:.1f} us", flush=True)
