@@ -225,6 +225,9 @@ SIGNATURES = {
     "ddpm_resample2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ddpm_softmax_rows_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "ddpm_softmax_backward_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    # ---- attention of the training step without an N x N tensor (additive: the ABI version stays)
+    "ddpm_attention_train_fwd_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
+    "ddpm_attention_train_bwd_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "ddpm_mse_loss_grad_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_float, C.c_void_p]),
     "ddpm_fill_f32": (C.c_int, [C.c_void_p, C.c_float, C.c_int64, C.c_void_p]),
     "ddpm_randn_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),

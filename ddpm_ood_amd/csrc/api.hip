@@ -374,3 +374,14 @@ extern "C" int ddpm_attention_ws_f32(const float *qkv, const float *residual, fl
                                      float scale, float *scratch, size_t scratch_floats, ddpm_stream_t stream) {
   return launch_attention(qkv, residual, out, B, C, N, num_heads, scale, as_stream(stream), scratch, scratch_floats);
 }
+
+extern "C" int ddpm_attention_train_fwd_f32(const float *q, const float *k, const float *v, float *o, float *lse, int B, int C, int N,
+                                            int num_heads, float scale, ddpm_stream_t stream) {
+  return launch_attention_train_fwd(q, k, v, o, lse, B, C, N, num_heads, scale, as_stream(stream));
+}
+
+extern "C" int ddpm_attention_train_bwd_f32(const float *q, const float *k, const float *v, const float *o, const float *dout,
+                                            const float *lse, float *delta, float *dq, float *dk, float *dv, int B, int C, int N,
+                                            int num_heads, float scale, ddpm_stream_t stream) {
+  return launch_attention_train_bwd(q, k, v, o, dout, lse, delta, dq, dk, dv, B, C, N, num_heads, scale, as_stream(stream));
+}

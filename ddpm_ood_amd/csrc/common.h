@@ -323,6 +323,12 @@ size_t attention_fa_scratch_floats(int B, int C, int N, int heads);
 bool attention_fa_supported(int B, int C, int N, int heads, const float *scratch, size_t scratch_floats);
 int launch_attention_fa(const float *qkv, const float *residual, float *out, int B, int C, int N, int heads, float scale,
                         float *scratch, hipStream_t s);
+// attention_train.hip: the training step's attention without an N x N tensor (forward + row statistic; delta, dq, dk / dv)
+int launch_attention_train_fwd(const float *q, const float *k, const float *v, float *o, float *lse, int B, int C, int N, int heads,
+                               float scale, hipStream_t s);
+int launch_attention_train_bwd(const float *q, const float *k, const float *v, const float *o, const float *dout, const float *lse,
+                               float *delta, float *dq, float *dk, float *dv, int B, int C, int N, int heads, float scale,
+                               hipStream_t s);
 int launch_timestep_embedding(const int64_t *t, const float *freqs, float *out, int B, int dim, hipStream_t s);
 int launch_copy_f32(const float *src, float *dst, int64_t n, hipStream_t s);
 

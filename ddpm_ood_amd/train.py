@@ -205,7 +205,7 @@ class DDPMTrainer(BaseTrainer):
         t_dev = timesteps.to(self.device)
         if backward:
             return self.stepper.loss_and_grads(noisy, t_dev, noise)
-        loss, _ = T.mse_loss_grad(self.stepper.forward(noisy, t_dev), noise)
+        loss, _ = T.mse_loss_grad(self.stepper.forward(noisy, t_dev, keep_tape=False), noise)  # validation: no tape
         return loss
 
     def _dist_all(self, fn, flat, **kw):

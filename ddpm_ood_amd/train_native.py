@@ -11,13 +11,15 @@ the updated parameters; ``torch.empty`` only asks the caching allocator for memo
 Forward (activations kept for the backward):
   GroupNorm statistics + a MATERIALISED GroupNorm/SiLU output (ddpm_gn_forward_f32: one kernel) -> the inference path's
   convolution kernels (ddpm_conv_f32: split-f16 F(4x4) Winograd where a launch fills the chip, its bias / temb / residual
-  epilogue), attention as two batched GEMMs around a row softmax (the probabilities are kept).
+  epilogue), attention as two batched GEMMs around a row softmax (the probabilities are kept) -- or, DDPM_TRAIN_ATTN=recompute,
+  ddpm_attention_train_fwd_f32: the output and one log-sum-exp per row, no N x N tensor.
 Backward (on the loss gradient times a power of two -- 1e-6-sized gradients are below f16's normal range --, the factor taken out
 of the flat gradient buffer by ddpm_scale_check_f32, which also flags an overflow; see loss_and_grads):
   3x3 / 1x1 input gradients = ddpm_conv_f32 with the weights rotated by 180 degrees and transposed; Downsample through a
   zero-stuffed dY; Upsample followed by a 2x2 sum; 3x3 weight gradients on ddpm_conv_wgrad_f32 (f16 MFMA at split precision,
   64 x 64 x 9 taps per workgroup; its operand maxima and the bias / temb plane sums come from the GroupNorm kernels that wrote the
-  operands); every other contraction (Linear / 1x1 weight and input gradients, the five attention products) on ddpm_gemm_f32;
+  operands); every other contraction (Linear / 1x1 weight and input gradients, the five attention products) on ddpm_gemm_f32
+  (recompute: ddpm_attention_train_bwd_f32 rebuilds the probabilities block by block in registers);
   GroupNorm + SiLU backward, bias sums, SiLU backward, softmax backward, MSE, Adam in train_ops.hip.
 """
 
@@ -43,6 +45,18 @@ def native_supported(model) -> bool:
         return True
     return (sd == 3 and model.in_channels % 64 == 0 and model.out_channels % 128 == 0
             and all(c % 128 == 0 for c in model.block_out_channels))
+
+
+class _Tape(list):
+    """The forward's record for the backward; with keep=False it records nothing."""
+
+    def __init__(self, keep: bool = True):
+        super().__init__()
+        self.keep = keep
+
+    def append(self, item):
+        if self.keep:
+            super().append(item)
 
 
 class NativeUNetStep:
@@ -81,6 +95,14 @@ class NativeUNetStep:
         # operand maxima / plane sums taken from the GroupNorm kernels that wrote the tensors (0: every consumer reads them again; A/B)
         self.fused_stats = os.environ.get("DDPM_TRAIN_FUSED_STATS", "1") != "0"
         self.conv1_dgrad_conv = os.environ.get("DDPM_TRAIN_1X1_DGRAD", "conv") != "gemm"
+        # the attention core: "gemm" = two / five strided GEMMs around row-softmax kernels, the fp32 [B heads, N, N] probabilities on
+        # the tape; "recompute" = the flash-attention pair of T.attention_fwd / T.attention_bwd (q, k, v, o and one statistic per row
+        # on the tape) for every block whose shape those kernels take, decided per block -- the others keep the GEMM route
+        self.attn_route = os.environ.get("DDPM_TRAIN_ATTN", "gemm")
+        if self.attn_route not in ("gemm", "recompute"):
+            raise ValueError(f"DDPM_TRAIN_ATTN={self.attn_route!r}: expected gemm or recompute")
+        self.attn_routes = []          # the last forward's attention blocks in call order: (route, heads, tokens)
+        self._tape = None
         self._flatten()
 
     # ---- flat parameter / gradient / moment buffers ----------------------------------------------------------------------
@@ -274,6 +296,12 @@ class NativeUNetStep:
         q = self._conv(xn, blk.to_q.weight, blk.to_q.bias)
         k = self._conv(xn, blk.to_k.weight, blk.to_k.bias)
         v = self._conv(xn, blk.to_v.weight, blk.to_v.bias)
+        recompute = self.attn_route == "recompute" and T.attention_takes(Cc, n, heads)
+        self.attn_routes.append(("recompute" if recompute else "gemm", heads, n))
+        if recompute:
+            o3, lse = T.attention_fwd(q.view(B, Cc, n), k.view(B, Cc, n), v.view(B, Cc, n), heads, scale)
+            o = o3.view(x.shape)
+            return self._attn_out(blk, x, o, (c, xn, q, k, v, None, o, lse, heads, d, scale))
         P = torch.empty((B * heads, n, n), dtype=torch.float32, device=x.device)
         zb = dict(batch=B * heads, batch_inner=heads, a_batch=d * n, a_batch_outer=Cc * n, b_batch=d * n, b_batch_outer=Cc * n)
         # S[z, i, j] = scale sum_c q[z, c, i] k[z, c, j]
@@ -284,16 +312,20 @@ class NativeUNetStep:
         # o[z, c, i] = sum_j v[z, c, j] P[z, i, j]
         T.gemm(v, P, o, d, n, n, a_m=n, a_k=1, b_k=1, b_n=n, c_m=n, c_n=1, batch=B * heads, batch_inner=heads, a_batch=d * n,
                a_batch_outer=Cc * n, b_batch=n * n, b_batch_outer=heads * n * n, c_batch=d * n, c_batch_outer=Cc * n)
+        return self._attn_out(blk, x, o, (c, xn, q, k, v, P, None, None, heads, d, scale))
+
+    def _attn_out(self, blk, x, o, core):
+        """proj_attn and the residual behind either core; the tape entry (blk, core context, proj_attn's input or None)."""
         if self.model.use_proj_attn:
             o_in = o
             o = self._conv(o_in, blk.proj_attn.weight, blk.proj_attn.bias)
         else:
             o_in = None
         out = T.axpby(o, x, 1.0, 1.0)
-        return out, (blk, c, xn, q, k, v, P, o_in, heads, d, scale)
+        return out, (blk,) + core + (o_in,)
 
     def _attn_bwd(self, ctx, dout):
-        blk, c, xn, q, k, v, P, o_in, heads, d, scale = ctx
+        blk, c, xn, q, k, v, P, o_core, lse, heads, d, scale, o_in = ctx
         B, Cc = dout.shape[:2]
         n = dout[0, 0].numel()
         do = dout
@@ -301,6 +333,10 @@ class NativeUNetStep:
             self._conv1_wgrad(o_in, blk.proj_attn.weight, dout)
             self._bias_grad(dout, blk.proj_attn.bias)
             do = self._conv1_dgrad(blk.proj_attn.weight, dout, None, accumulate=False)
+        if P is None:  # the recompute route: no tensor with N x N elements, here or on the tape
+            f3 = lambda t: t.view(B, Cc, n)  # noqa: E731
+            dq, dk, dv = (t.view(q.shape) for t in T.attention_bwd(f3(q), f3(k), f3(v), f3(o_core), f3(do), lse, heads, scale))
+            return self._attn_proj_bwd(blk, c, xn, dq, dk, dv, dout)
         zq = dict(batch=B * heads, batch_inner=heads)
         cn = dict(c_m=n, c_n=1)
         dv, dq, dk = torch.empty_like(v), torch.empty_like(q), torch.empty_like(k)
@@ -318,6 +354,10 @@ class NativeUNetStep:
         # dk[z, c, j] = scale sum_i dS[z, i, j] q[z, c, i]
         T.gemm(q, dP, dk, d, n, n, a_m=n, a_k=1, b_k=n, b_n=1, a_batch=d * n, a_batch_outer=Cc * n, b_batch=n * n,
                b_batch_outer=heads * n * n, c_batch=d * n, c_batch_outer=Cc * n, alpha=scale, **cn, **zq)
+        return self._attn_proj_bwd(blk, c, xn, dq, dk, dv, dout)
+
+    def _attn_proj_bwd(self, blk, c, xn, dq, dk, dv, dout):
+        """The q / k / v projections, the GroupNorm and the residual behind either core."""
         dxn = torch.empty_like(xn)
         for i, (lin, dt) in enumerate(((blk.to_q, dq), (blk.to_k, dk), (blk.to_v, dv))):
             self._conv1_wgrad(xn, lin.weight, dt)
@@ -328,9 +368,13 @@ class NativeUNetStep:
         return dx
 
     # ---- the network ----------------------------------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, timesteps: torch.Tensor, keep_tape: bool = True) -> torch.Tensor:
+        """keep_tape=False: the same launches and the same bits, but nothing is kept for a backward -- each block's activations
+        are released as the forward moves on, and a tape left by an earlier forward is dropped (validation)."""
         m = self.model
-        tape = []
+        tape = _Tape(keep_tape)
+        self._tape = None
+        self.attn_routes = []
         ch0 = m.block_out_channels[0]
         if ch0 % 2:
             raise NotImplementedError("odd num_channels[0]")
@@ -390,7 +434,7 @@ class NativeUNetStep:
         oc = m.out[2].conv
         tape.append(("out", (oc, a, c)))
         pred = self._conv(a, oc.weight, oc.bias)
-        self._tape = tape
+        self._tape = tape if keep_tape else None
         return pred
 
     def backward(self, dpred: torch.Tensor) -> None:

@@ -263,6 +263,61 @@ def softmax_backward_rows_(p, dp, rows: int, cols: int):
     return dp
 
 
+ATTN_HEAD_DIM = 256  # the one head dim attention_fwd / attention_bwd take (kD of csrc/attention_train.hip)
+
+
+def attention_takes(C_: int, n: int, heads: int) -> bool:
+    """Do attention_fwd / attention_bwd take [B, C_, n] with this many heads (head dim 256, n a positive multiple of 64)?"""
+    return heads > 0 and C_ == heads * ATTN_HEAD_DIM and n > 0 and n % 64 == 0
+
+
+def _attn_args(what, heads, tensors):
+    """Device fp32 contiguous [B, heads * 256, N] tensors of one shape; returns (B, C, N)."""
+    shape = None
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a ROCm device tensor (no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if t.ndim != 3:
+            raise ValueError(f"{what}: {name} must be [B, C, N], got {tuple(t.shape)}")
+        if shape is None:
+            shape = tuple(t.shape)
+        elif tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {name} is {tuple(t.shape)}, expected {shape}")
+    B, C_, n = shape
+    if not attention_takes(C_, n, heads):
+        raise ValueError(f"{what}: [B, C, N] = {shape} with {heads} heads: needs C = heads * {ATTN_HEAD_DIM} and N a positive "
+                         "multiple of 64")
+    return B, C_, n
+
+
+def attention_fwd(q, k, v, heads: int, scale: float):
+    """(o, lse) of o = softmax(scale q^T k) v per head over [B, heads * 256, N] tensors; lse [B, heads, N] is the log-sum-exp of
+    each row of scores -- what attention_bwd needs instead of the N x N probabilities."""
+    B, C_, n = _attn_args("attention_fwd", heads, {"q": q, "k": k, "v": v})
+    o, lse = torch.empty_like(q), _empty((B, heads, n), q)
+    check(_lib.load().ddpm_attention_train_fwd_f32(ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), B, C_, n, heads, scale, stream_ptr()),
+          "attention_fwd")
+    return o, lse
+
+
+def attention_bwd(q, k, v, o, do, lse, heads: int, scale: float):
+    """(dq, dk, dv) from the forward's inputs, its output o, the output gradient do and the row statistic lse; the probabilities
+    are recomputed block by block inside the kernels."""
+    B, C_, n = _attn_args("attention_bwd", heads, {"q": q, "k": k, "v": v, "o": o, "do": do})
+    if not isinstance(lse, torch.Tensor) or not lse.is_cuda or lse.dtype != torch.float32 or not lse.is_contiguous() \
+            or tuple(lse.shape) != (B, heads, n):
+        raise ValueError(f"attention_bwd: lse must be a contiguous float32 device tensor [{B}, {heads}, {n}]")
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = torch.empty_like(lse)
+    check(_lib.load().ddpm_attention_train_bwd_f32(ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), ptr(delta), ptr(dq), ptr(dk),
+                                                   ptr(dv), B, C_, n, heads, scale, stream_ptr()), "attention_bwd")
+    return dq, dk, dv
+
+
 def mse_loss_grad(pred, target):
     """(loss [1] on the device, dpred) of F.mse_loss(pred, target)."""
     n = pred.numel()

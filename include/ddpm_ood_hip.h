@@ -852,6 +852,24 @@ int ddpm_resample3_f32(const float *in, float *out, int64_t planes, int D, int H
 /* softmax over each row in place; its backward ds = p (dp - sum(dp p)) in place over dp  */
 int ddpm_softmax_rows_f32(float *s_inout, int64_t rows, int cols, ddpm_stream_t stream);
 int ddpm_softmax_backward_rows_f32(const float *p, float *dp_inout, int64_t rows, int cols, ddpm_stream_t stream);
+/* Attention of the training step without an N x N tensor (additive: the ABI version stays).  The core of
+ * generative's AttentionBlock, o = softmax(scale q^T k) v per head, over q, k, v, o, do, dq, dk, dv of B * C * N floats each, laid
+ * out [B, C, N] as the 1x1 projections write them; head h owns channels 256 h .. 256 h + 255 (C = heads * 256: head dim 256 only),
+ * N a positive multiple of 64, B * C * N < 2^31.  lse and delta are B * heads * N floats each, [B, heads, N].  No workspace.
+ *   forward:  o, and lse[b, h, i] = max_j s_ij + log sum_j exp(s_ij - max), s = scale q_i . k_j -- one float per row instead of
+ *             the N probabilities.
+ *   backward: delta[b, h, i] = sum_c do[c, i] o[c, i] (written first, then read: caller memory so that the call allocates nothing;
+ *             the dq kernel then moves it by (sum_j ds_ij) / (sum_j p_ij), a rounding-level step after which dk sums to zero over j),
+ *             p_ij = exp(s_ij - lse_i) recomputed per 32-token block, ds_ij = p_ij (do_i . v_j - delta_i),
+ *             dq_i = scale sum_j ds_ij k_j,  dk_j = scale sum_i ds_ij q_i,  dv_j = sum_i p_ij do_i.
+ * Exact fp32 products on the fp32 MFMA (no operand-range condition on q, k, v or do); scores, probabilities and ds stay in
+ * registers.  Every output element is written once by a plain store in a fixed summation order.  Inputs must be 16-byte
+ * aligned.  -1 with a message: a null pointer, C != heads * 256, N not a positive multiple of 64, an extent past 32-bit indexing.  */
+int ddpm_attention_train_fwd_f32(const float *q, const float *k, const float *v, float *o, float *lse, int B, int C, int N,
+                                 int num_heads, float scale, ddpm_stream_t stream);
+int ddpm_attention_train_bwd_f32(const float *q, const float *k, const float *v, const float *o, const float *dout, const float *lse,
+                                 float *delta, float *dq, float *dk, float *dv, int B, int C, int N, int num_heads, float scale,
+                                 ddpm_stream_t stream);
 /* F.mse_loss(pred, target): dpred = grad_scale (pred - target) (grad_scale = 2 / n), partial[i] = sum of (pred - target)^2
  * over elements [256 i, 256 i + 256): the caller sums ceil(n / 256) partials (ddpm_col_sum_f32) and divides by n.  */
 int ddpm_mse_loss_grad_f32(const float *pred, const float *target, float *dpred, float *partial, int64_t n, float grad_scale,

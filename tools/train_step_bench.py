@@ -1,6 +1,7 @@
-"""Training-step throughput of the `small` UNet on one MI355X: the native step (train_native.NativeUNetStep -- hand-written HIP forward /
+"""Training-step throughput of a UNet (default: `small` on 1 x 32 x 32) on one MI355X: the native step (train_native.NativeUNetStep -- hand-written HIP forward /
 backward / Adam) beside the ATen route (PyTorch-ROCm autograd over MIOpen / rocBLAS, DDPM_TRAIN_NATIVE=0), same weights, same batch.
-    python tools/train_step_bench.py [batch] [steps] [native|aten|amp|both|all]
+    python tools/train_step_bench.py [batch] [steps] [native|aten|amp|both|all] [model type] [image size] [channels]
+(`... 2 5 native big 64 3` under DDPM_TRAIN_ATTN=gemm and =recompute: the attention routes of DESIGN 3.28 on the `big` UNet.)
 (amp: the ATen route under fp16 autocast + GradScaler -- the reference's own training arithmetic, ddpm_trainer.py:96-109.)
 Row f-3 (/root/reference/src/trainers/ddpm_trainer.py:78-109, base.py:156).  `rocprofv3 --kernel-trace --stats -- python
 tools/train_step_bench.py 64 5 native` is the profile committed as profiles/r06_train_native_kernel_trace_stats.csv."""
@@ -22,14 +23,17 @@ from ddpm_ood_amd.trainer import MODEL_CONFIGS  # noqa: E402
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 which = sys.argv[3] if len(sys.argv) > 3 else "both"
+model_type = sys.argv[4] if len(sys.argv) > 4 else "small"
+size = int(sys.argv[5]) if len(sys.argv) > 5 else 32
+chans = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 dev = torch.device("cuda:0")
-sd = random_state_dict("small", 1, seed=1)
-x = torch.rand(B, 1, 32, 32, device=dev)
+sd = random_state_dict(model_type, chans, seed=1)
+x = torch.rand(B, chans, size, size, device=dev)
 t = torch.randint(0, 1000, (B,)).to(dev)
 
 
 def model():
-    m = DiffusionModelUNet(2, 1, 1, **MODEL_CONFIGS["small"])
+    m = DiffusionModelUNet(2, chans, chans, **MODEL_CONFIGS[model_type])
     m.load_state_dict(sd)
     return m.to(dev).train()
 
@@ -52,7 +56,7 @@ if which in ("native", "both", "all"):
 
         def native_step():
             k[0] += 1
-            noise = T.randn((B, 1, 32, 32), dev, 1, k[0])
+            noise = T.randn((B, chans, size, size), dev, 1, k[0])
             st.loss_and_grads(x, t, noise)
             st.adam_step()
 
@@ -78,7 +82,9 @@ if which in ("native", "both", "all"):
                 print(f"{kname:64s} {v['launches']:6d} {v['ms']:9.3f} {100 * v['ms'] / tot:6.1f} "
                       f"{v['flops'] / v['ms'] / 1e9 if v['ms'] else 0:8.1f} {v['bytes'] / v['ms'] / 1e6 if v['ms'] else 0:8.1f}")
             print(f"{'sum':64s} {'':6s} {tot:9.3f}")
-    print(f"native: batch {B}: {dt * 1e3:.2f} ms per step = {B / dt:.0f} images/s")
+    routes = sorted({r for r, _, _ in st.attn_routes})
+    print(f"native ({model_type} {chans} x {size} x {size}, attention {'+'.join(routes)}): batch {B}: {dt * 1e3:.2f} ms per step = "
+          f"{B / dt:.0f} images/s, peak {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
 if which in ("aten", "both", "all"):
     m = model()
     for p in m.parameters():
@@ -86,7 +92,7 @@ if which in ("aten", "both", "all"):
     opt = torch.optim.Adam(m.parameters(), lr=2.5e-5)
 
     def aten_step():
-        noise = torch.randn(B, 1, 32, 32, device=dev)
+        noise = torch.randn(B, chans, size, size, device=dev)
         opt.zero_grad(set_to_none=True)
         loss = torch.nn.functional.mse_loss(unet_forward_torch(m, x, t), noise)
         loss.backward()
@@ -102,7 +108,7 @@ if which in ("amp", "all"):
     scaler = torch.amp.GradScaler("cuda")
 
     def amp_step():
-        noise = torch.randn(B, 1, 32, 32, device=dev)
+        noise = torch.randn(B, chans, size, size, device=dev)
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.float16):
             loss = torch.nn.functional.mse_loss(unet_forward_torch(m, x, t).float(), noise)
