@@ -154,6 +154,10 @@ SIGNATURES = {
     "ddpm_map_zscore_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p]),
     "ddpm_map_zscore_loo_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_void_p]),
     "ddpm_map_blur_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    # ---- anomaly maps of volumes (additive: the ABI version stays)
+    "ddpm_map_blur3d_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
+    "ddpm_lpips_map_upsample_view_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_int] * 15
+                                         + [C.c_float, C.c_int, C.c_void_p]),
     # ---- pixel-level metrics of the maps against masks (additive: the ABI version stays)
     "ddpm_map_mask_hist_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -207,6 +207,122 @@ __global__ __launch_bounds__(256) void lpips_map_upsample_kernel(const float *__
   }
 }
 
+// ---- the LPIPS map of a volume (2.5-D: DESIGN 3.29) ---------------------------------------------------------------------------
+// out[n, d, h, w] (+)= weight * the resampled layer sum, at the voxel's in-plane position, of the slice the voxel lies in, for
+// the slices taken along `axis` of [N, C, D, H, W] (rows: [N * S, row_stride], volume-major, S the extent along the axis).
+// The per-layer expressions and the order of the layer sum are lpips_map_upsample_kernel's, so a voxel carries the bits that
+// kernel gives for the same slice.  A wave owns 64 adjacent w of one (n, d) and walks kViewChunk rows h: every store is one
+// contiguous run of 64 floats along w, for every axis.  What a voxel's coordinates mean depends on the axis:
+//   axis 2   slice d, plane position (h, w): the column pair and weight belong to the lane and are formed once per walk; the row
+//            pair changes with h and is the same for the whole wave;
+//   axis 3   slice h, plane position (d, w): row and column pairs are both fixed along the walk, the packed row changes with h;
+//   axis 4   slice w -- a lane owns a SLICE -- plane position (d, h): the row pair is fixed, the column pair changes with h and
+//            is the same for the whole wave.  A layer's four samples stay in registers and are read again only when the column
+//            pair moves (once every H / w_k steps; a wave-uniform branch).  The loads are strided by the packed row (a few KB per
+//            slice, L2-resident).
+// The pairs that change with h are formed ONCE per walk, one (layer, step) per lane (5 layers x 12 steps = 60 lanes), and handed
+// to the wave step by step with v_readlane: a thread per voxel that forms both pairs of every layer itself (about 500
+// instructions per voxel, most of them index arithmetic) took 29 us at 128^3, this form 21 (profiles/anomaly_volume_maps.md).
+constexpr int kViewChunk = 12;  // h positions a wave walks: 5 layers x 12 (layer, step) pairs fit the 64 lanes
+
+__device__ __forceinline__ int view_pick(const int (&v)[5], int k) {  // v[k] without indexing the kernel argument dynamically
+  int r = v[0];
+#pragma unroll
+  for (int j = 1; j < 5; ++j) r = k == j ? v[j] : r;
+  return r;
+}
+
+template <int AXIS>
+__global__ __launch_bounds__(256) void lpips_map_view_kernel(const float *__restrict__ maps, float *__restrict__ out,
+                                                             const LpipsMapLayers L, int64_t row_stride, int D, int H, int W,
+                                                             int w_tiles, int h_chunks, int64_t jobs, float weight, int accumulate) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  int64_t job = blockIdx.x * (int64_t)4 + wave;  // (n, d, h chunk, w tile): one per wave, wave-uniform
+  if (job >= jobs) return;
+  const int wt = (int)(job % w_tiles);
+  job /= w_tiles;
+  const int hc = (int)(job % h_chunks);
+  job /= h_chunks;
+  const int d = (int)(job % D);
+  const int64_t n = job / D;
+  const int w = wt * 64 + lane;
+  const bool live = w < W;
+  const int wc = live ? w : W - 1;  // a dead lane computes its tile's last column and stores nothing
+  const int h_begin = hc * kViewChunk, steps = min(kViewChunk, H - h_begin);
+  // the pair that changes along the walk, one (layer, step) per lane: rows of the plane (axis 2) or its columns (axis 4)
+  int pi0 = 0, pi1 = 0;
+  float pl = 0.f;
+  if (AXIS != 3) {
+    const int k = lane / kViewChunk;
+    if (k < L.n) {
+      const int ext = AXIS == 2 ? view_pick(L.h, k) : view_pick(L.w, k);
+      bilinear_axis(min(h_begin + lane % kViewChunk, H - 1), ext, (float)ext / (float)H, pi0, pi1, pl);
+    }
+  }
+  // what is fixed along the walk: f = the columns of w (axis 2) or the rows of d (axes 3, 4); g = the columns of w (axis 3)
+  int f0[5], f1[5], g0[5], g1[5];
+  float fl[5], gl[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    f0[k] = f1[k] = g0[k] = g1[k] = 0;
+    fl[k] = gl[k] = 0.f;
+    if (k < L.n) {
+      if (AXIS == 2) bilinear_axis(wc, L.w[k], (float)L.w[k] / (float)W, f0[k], f1[k], fl[k]);
+      else bilinear_axis(d, L.h[k], (float)L.h[k] / (float)D, f0[k], f1[k], fl[k]);
+      if (AXIS == 3) bilinear_axis(wc, L.w[k], (float)L.w[k] / (float)W, g0[k], g1[k], gl[k]);
+    }
+  }
+  const float *row = maps + (AXIS == 2 ? n * D + d : AXIS == 3 ? n * H : n * W + wc) * row_stride;
+  int px0[5], px1[5];
+  float m00[5], m01[5], m10[5], m11[5];  // axis 4: the samples held across steps
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    px0[k] = px1[k] = -1;
+    m00[k] = m01[k] = m10[k] = m11[k] = 0.f;
+  }
+  // unrolled over the whole chunk with h clamped: the steps are straight-line code, the loads of several steps can be in flight
+  // together, and only the store is guarded
+#pragma unroll
+  for (int s = 0; s < kViewChunk; ++s) {
+    const int h = min(h_begin + s, H - 1);
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      if (k < L.n) {
+        const int lw = L.w[k];
+        int y0, y1, x0, x1;
+        float ly, lx;
+        if (AXIS == 3) {
+          y0 = f0[k], y1 = f1[k], ly = fl[k], x0 = g0[k], x1 = g1[k], lx = gl[k];
+        } else {
+          const int sel = k * kViewChunk + s;
+          const int q0 = __builtin_amdgcn_readlane(pi0, sel), q1 = __builtin_amdgcn_readlane(pi1, sel);
+          const float ql = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl), sel));
+          if (AXIS == 2) y0 = q0, y1 = q1, ly = ql, x0 = f0[k], x1 = f1[k], lx = fl[k];
+          else y0 = f0[k], y1 = f1[k], ly = fl[k], x0 = q0, x1 = q1, lx = ql;
+        }
+        const float *m = row + (AXIS == 3 ? (int64_t)h * row_stride : 0) + L.off[k];
+        if (AXIS != 4 || x0 != px0[k] || x1 != px1[k]) {
+          m00[k] = m[y0 * lw + x0];
+          m01[k] = m[y0 * lw + x1];
+          m10[k] = m[y1 * lw + x0];
+          m11[k] = m[y1 * lw + x1];
+          px0[k] = x0;
+          px1[k] = x1;
+        }
+        const float top = (1.f - lx) * m00[k] + lx * m01[k];
+        const float bot = (1.f - lx) * m10[k] + lx * m11[k];
+        acc += (1.f - ly) * top + ly * bot;
+      }
+    }
+    if (live && s < steps) {
+      const int64_t i = ((n * D + d) * H + h) * W + w;
+      out[i] = accumulate ? out[i] + weight * acc : weight * acc;
+    }
+  }
+}
+
 // ---- the 5x5 layer on the fp32 MFMA pipe -------------------------------------------------------------------------------
 // For 2.5-D LPIPS over 128^3 volumes (cfg5: 128 slices x 3 views x 2 inputs per volume and t-start) the 5x5 layer
 // (64 -> 192 over 15 x 15) is 35 GFLOP per call and the scalar kernel above ran it at 9 TFLOP/s -- a quarter of a
@@ -433,9 +549,62 @@ int launch_lpips_map_upsample(const float *maps, float *out, int N, int64_t row_
   return 0;
 }
 
+int launch_lpips_map_upsample_view(const float *maps, float *out, int N, int64_t row_stride, const LpipsMapLayers &L, int D, int H,
+                                   int W, int axis, float weight, int accumulate, hipStream_t s) {
+  DDPM_CHECK_ARG(maps && out, "lpips_map_upsample_view: null pointer");
+  DDPM_CHECK_ARG(N > 0 && row_stride > 0, "lpips_map_upsample_view: N and row_stride must be positive");
+  DDPM_CHECK_ARG(axis >= 2 && axis <= 4, "lpips_map_upsample_view: axis must be 2, 3 or 4 of [N, C, D, H, W] (got %d)", axis);
+  DDPM_CHECK_ARG(L.n >= 1 && L.n <= 5, "lpips_map_upsample_view: n_layers must be 1 .. 5 (got %d)", L.n);
+  for (int k = 0; k < L.n; ++k)
+    DDPM_CHECK_ARG(L.h[k] > 0 && L.w[k] > 0 && L.h[k] <= 4096 && L.w[k] <= 4096,
+                   "lpips_map_upsample_view: layer %d has the extent %d x %d", k, L.h[k], L.w[k]);
+  DDPM_CHECK_ARG((int64_t)L.off[L.n - 1] + L.h[L.n - 1] * L.w[L.n - 1] <= row_stride,
+                 "lpips_map_upsample_view: the layers do not fit a row of %lld", (long long)row_stride);
+  DDPM_CHECK_ARG(D > 0 && H > 0 && W > 0 && D <= (1 << 20) && H <= (1 << 20) && W <= (1 << 20),
+                 "lpips_map_upsample_view: extents 1 .. 2^20 (got %d x %d x %d)", D, H, W);
+  const double total_d = (double)N * D * (double)H * W;
+  DDPM_CHECK_ARG(total_d < 9.0e18, "lpips_map_upsample_view: volume too large");
+  const int S = axis == 2 ? D : axis == 3 ? H : W;
+  DDPM_CHECK_ARG(!lp_overlap(out, 4.0 * total_d, maps, 4.0 * N * S * (double)row_stride), "lpips_map_upsample_view: out aliases maps");
+  ProfScope prof(s, "lpips_map_upsample_view", 12.0 * total_d * L.n, 4.0 * total_d * (accumulate ? 2 : 1) + 4.0 * N * S * (double)row_stride);
+  const int w_tiles = (W + 63) / 64, h_chunks = (H + kViewChunk - 1) / kViewChunk;
+  const double jobs_d = (double)N * D * (double)h_chunks * w_tiles;
+  DDPM_CHECK_ARG(jobs_d < 4.0 * 2147483647.0, "lpips_map_upsample_view: too many tiles");
+  const int64_t jobs = (int64_t)N * D * h_chunks * w_tiles;
+  const dim3 grid((unsigned)((jobs + 3) / 4));
+  if (axis == 2)
+    hipLaunchKernelGGL(lpips_map_view_kernel<2>, grid, dim3(256), 0, s, maps, out, L, row_stride, D, H, W, w_tiles, h_chunks, jobs,
+                       weight, accumulate);
+  else if (axis == 3)
+    hipLaunchKernelGGL(lpips_map_view_kernel<3>, grid, dim3(256), 0, s, maps, out, L, row_stride, D, H, W, w_tiles, h_chunks, jobs,
+                       weight, accumulate);
+  else
+    hipLaunchKernelGGL(lpips_map_view_kernel<4>, grid, dim3(256), 0, s, maps, out, L, row_stride, D, H, W, w_tiles, h_chunks, jobs,
+                       weight, accumulate);
+  DDPM_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace ddpm
 
 using namespace ddpm;
+
+static LpipsMapLayers lp_packed_layers(int n_layers, int h0, int w0, int h1, int w1, int h2, int w2, int h3, int w3, int h4, int w4) {
+  LpipsMapLayers L{n_layers, {h0, h1, h2, h3, h4}, {w0, w1, w2, w3, w4}, {0, 0, 0, 0, 0}};
+  // layer k of a row starts where layer k - 1 ends; extents beyond the launcher's limits (which it refuses) count as 0 here
+  for (int k = 1; k < 5 && k < n_layers; ++k) {
+    const bool ok = L.h[k - 1] > 0 && L.w[k - 1] > 0 && L.h[k - 1] <= 4096 && L.w[k - 1] <= 4096;
+    L.off[k] = L.off[k - 1] + (ok ? L.h[k - 1] * L.w[k - 1] : 0);
+  }
+  return L;
+}
+
+extern "C" int ddpm_lpips_map_upsample_view_f32(const float *maps, float *out, int N, int64_t row_stride, int n_layers, int h0,
+                                                int w0, int h1, int w1, int h2, int w2, int h3, int w3, int h4, int w4, int D,
+                                                int H, int W, int axis, float weight, int accumulate, ddpm_stream_t stream) {
+  return launch_lpips_map_upsample_view(maps, out, N, row_stride, lp_packed_layers(n_layers, h0, w0, h1, w1, h2, w2, h3, w3, h4, w4),
+                                        D, H, W, axis, weight, accumulate, as_stream(stream));
+}
 
 extern "C" int ddpm_lpips_layer_map_f32(const float *f0, const float *f1, const float *lin, float *maps, int N, int C, int HW,
                                         int64_t row_stride, int64_t row_offset, ddpm_stream_t stream) {

@@ -308,9 +308,105 @@ int launch_map_blur(const float *in, float *out, const float *taps, int radius, 
   return 0;
 }
 
+// ---- 3-D smoothing: the two in-plane passes above over the N D planes, then the depth pass --------------------------------------------
+// Depth pass: out[n, d, c] = sum_k taps[k] in[n, refl(d + k - radius, D), c] over the columns c of the flattened plane (P = H W
+// of them: w runs across the lanes, so every load and store is a contiguous run of 64 floats).  A workgroup of four waves owns
+// 64 adjacent columns and streams down D in steps of 32 planes.  The window lives in an LDS ring of 128 rows x 64 columns (32 KB;
+// a lane reads its own column: bank = lane, no conflict): the row of virtual depth j (-radius <= j < D + radius, read from
+// plane refl(j, D)) sits in slot (j + radius) mod 128 (counted from the workgroup's first plane).  A step adds its 32 new rows (eight per wave, fetched into registers
+// one step ahead, so 8 KB per workgroup fly during the arithmetic: with 16 rows per step the pass ran at 1.0 TB/s on one 128^3
+// volume pair, bound by the bytes in flight, profiles/anomaly_volume_maps.md), then every wave sums eight output planes.  One
+// barrier per step: the rows step i + 1 writes take the slots of rows below d0 - 64 + radius, which step i no longer reads, and a
+// wave reaches the writes of step i + 2 (slots of rows d0 - 64 + radius .. d0 - 33 + radius, all below d0 - radius) only behind
+// the barrier of step i + 1.  Every plane is read once from memory, the planes the reflection repeats at the two ends aside.
+// A workgroup's steps are one chain of dependent waits, so a launch with few column tiles (one 128^3 volume pair: 512) is bound by
+// that chain, not by bytes: while there are fewer than kDepthMinBlocks workgroups the launcher cuts D into segments of a multiple
+// of 32 planes, each streamed by a workgroup of its own (its 2 radius halo planes are read again, from the caches).  The bits
+// of an output do not depend on the cut.
+constexpr int kDepthCols = 64, kDepthStep = 32, kDepthRing = 128, kDepthWaves = 4, kDepthMinBlocks = 2048;
+static_assert(2 * kDepthStep + 2 * kBlurMaxRadius <= kDepthRing, "the depth ring must hold two steps and their halo");
+
+__global__ __launch_bounds__(256) void map_blur_depth_kernel(const float *__restrict__ in, float *__restrict__ out,
+                                                             const float *__restrict__ taps, int radius, int D, int64_t P,
+                                                             int64_t tiles, int seg, int segs) {
+  __shared__ float ring[kDepthRing * kDepthCols];
+  __shared__ float tap[2 * kBlurMaxRadius + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sg = (int)(blockIdx.x % segs);
+  const int64_t nt = blockIdx.x / segs, n = nt / tiles, tile = nt - n * tiles;
+  const int d_lo = sg * seg, d_hi = min(D, d_lo + seg);  // this workgroup's output planes
+  const int64_t c = tile * kDepthCols + lane;
+  const bool live = c < P;
+  const float *vin = in + n * D * P + (live ? c : 0);
+  float *vout = out + n * D * P + (live ? c : 0);
+  const int ntap = 2 * radius + 1, first = d_lo - radius, last = d_hi + radius;  // virtual rows first .. last - 1: slot (j - first) mod ring
+  if (tid < ntap) tap[tid] = taps[tid];
+  for (int j = first + wave; j < d_lo + radius; j += kDepthWaves)  // the halo above the first step's rows
+    ring[((j - first) & (kDepthRing - 1)) * kDepthCols + lane] = live ? vin[(int64_t)refl(j, D) * P] : 0.f;
+  constexpr int kPer = kDepthStep / kDepthWaves;
+  float next[kPer];
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) {  // the first step's own rows: radius .. radius + kDepthStep - 1
+    const int j = d_lo + radius + wave + q * kDepthWaves;
+    next[q] = live && j < last ? vin[(int64_t)refl(j, D) * P] : 0.f;
+  }
+  for (int d0 = d_lo; d0 < d_hi; d0 += kDepthStep) {
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+      const int j = d0 + radius + wave + q * kDepthWaves;
+      if (j < last) ring[((j - first) & (kDepthRing - 1)) * kDepthCols + lane] = next[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+      const int j = d0 + kDepthStep + radius + wave + q * kDepthWaves;
+      next[q] = live && j < last ? vin[(int64_t)refl(j, D) * P] : 0.f;
+    }
+    for (int d = d0 + wave; d < min(d0 + kDepthStep, d_hi); d += kDepthWaves) {
+      float acc = tap[0] * ring[((d - d_lo) & (kDepthRing - 1)) * kDepthCols + lane];  // virtual row d - radius: slot d - d_lo
+      for (int k = 1; k < ntap; ++k) acc += tap[k] * ring[((d - d_lo + k) & (kDepthRing - 1)) * kDepthCols + lane];
+      if (live) vout[(int64_t)d * P] = acc;
+    }
+  }
+}
+
+int launch_map_blur3d(const float *in, float *out, float *tmp, const float *taps, int radius, int N, int D, int H, int W,
+                      hipStream_t s) {
+  DDPM_CHECK_ARG(in && out && tmp && taps, "map_blur3d: null pointer");
+  DDPM_CHECK_ARG(radius >= 0, "map_blur3d: radius must not be negative (got %d)", radius);
+  DDPM_CHECK_ARG(radius <= kBlurMaxRadius, "map_blur3d: radius %d is above the maximum of %d (sigma < 4.125 at truncate 4)", radius,
+                 kBlurMaxRadius);
+  DDPM_CHECK_ARG(N > 0 && D > 0 && H > 0 && W > 0, "map_blur3d: N, D, H and W must be positive (got %d, %d, %d, %d)", N, D, H, W);
+  DDPM_CHECK_ARG(D <= (1 << 20) && H <= (1 << 20) && W <= (1 << 20), "map_blur3d: extents up to 2^20 (got %d x %d x %d)", D, H, W);
+  DDPM_CHECK_ARG((double)N * D < 2147483647.0, "map_blur3d: too many planes");
+  const int64_t P = (int64_t)H * W, tiles = (P + kDepthCols - 1) / kDepthCols;
+  DDPM_CHECK_ARG((double)N * (double)tiles < 2147483647.0, "map_blur3d: too many column tiles");
+  const double bytes = 4.0 * N * D * (double)P, t_bytes = 4.0 * (2 * radius + 1);
+  DDPM_CHECK_ARG(!zm_overlap(out, bytes, in, bytes) && !zm_overlap(out, bytes, taps, t_bytes) && !zm_overlap(tmp, bytes, in, bytes) &&
+                     !zm_overlap(tmp, bytes, out, bytes) && !zm_overlap(tmp, bytes, taps, t_bytes),
+                 "map_blur3d: out or tmp aliases another operand (in place is not built)");
+  const int rc = launch_map_blur(in, tmp, taps, radius, N * D, H, W, s);  // the H pass, then the W pass, plane by plane
+  if (rc != 0) return rc;
+  int seg = D;  // planes per workgroup: all of D, or a multiple of kDepthStep while the launch is short of workgroups
+  while (seg > kDepthStep && (double)N * (double)tiles * ((D + seg - 1) / seg) < kDepthMinBlocks)
+    seg = (seg / 2 + kDepthStep - 1) / kDepthStep * kDepthStep;
+  const int segs = (D + seg - 1) / seg;
+  DDPM_CHECK_ARG((double)N * (double)tiles * segs < 2147483647.0, "map_blur3d: too many workgroups");
+  ProfScope prof(s, "map_blur_depth", 2.0 * (2 * radius + 1) * N * D * (double)P, 2.0 * bytes);
+  hipLaunchKernelGGL(map_blur_depth_kernel, dim3((unsigned)(N * tiles * segs)), dim3(256), 0, s, tmp, out, taps, radius, D, P, tiles,
+                     seg, segs);
+  DDPM_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace ddpm
 
 using namespace ddpm;
+
+extern "C" int ddpm_map_blur3d_f32(const float *in, float *out, float *tmp, const float *taps, int radius, int N, int D, int H, int W,
+                                   ddpm_stream_t stream) {
+  return launch_map_blur3d(in, out, tmp, taps, radius, N, D, H, W, as_stream(stream));
+}
 
 extern "C" int ddpm_map_stats_update_f32(const float *values, int B, int64_t P, int64_t n_prev, float *mean, float *m2,
                                          ddpm_stream_t stream) {

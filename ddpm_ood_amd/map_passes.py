@@ -47,6 +47,22 @@ class MapSettings:
     sg_min_component: int = None
     sg_thresholds: list = None
     sg_connectivity: int = None
+    volume_maps: bool = False  # maps_<name>.npz of volumes [N, D, H, W]: 2.5-D LPIPS and squared error per voxel
+    volume_z_maps: bool = False  # map_stats.npz, zmaps_<name>.npz of volumes; --anomaly_z_sigma smooths in 3-D
+    volume_views: str = "last"  # the slice directions of the LPIPS map: the view whose value is the score, or all three
+    volume_budget: int = None  # bytes a batch's maps may take on the device
+
+    @property
+    def want_maps(self) -> bool:
+        return self.anomaly_maps or self.volume_maps
+
+    @property
+    def want_z_maps(self) -> bool:
+        return self.anomaly_z_maps or self.volume_z_maps
+
+    @property
+    def volume(self) -> bool:
+        return self.volume_maps or self.volume_z_maps
 
     @classmethod
     def from_args(cls, args):
@@ -61,6 +77,7 @@ class MapSettings:
                              "--vqvae_checkpoint): 2.5-D and latent maps are not built")
         if s["anomaly_z_maps"]:
             zmaps.check_flags(args.spatial_dimension, args.vqvae_checkpoint, s["z_sigma"], s["z_std_floor"])
+        s.update(check_volume_flags(args, s))
         bins = getattr(args, "pixel_bins", pixel_metrics.DEFAULT_BINS), getattr(args, "pixel_range", None) or pixel_metrics.DEFAULT_RANGE
         if s["pixel_metrics"]:
             s["px_lo"], s["px_hi"], s["px_bins"], s["px_thresholds"], s["px_masks"] = pixel_metrics.check_flags(
@@ -78,6 +95,48 @@ class MapSettings:
         if s["pixel_segment"]:
             s["sg_median"], s["sg_min_component"], s["sg_thresholds"], s["sg_connectivity"] = pixel_metrics.check_segment_flags(args)
         return cls(**s)
+
+
+VOLUME_VIEWS = ("last", "all")
+DEFAULT_VOLUME_BUDGET_GB = 8.0
+
+
+def check_volume_flags(args, s) -> dict:
+    """The volume flags' fields of ``MapSettings`` ({} with both off), or the refusals they earn, from the Namespace alone."""
+    on = {"volume_maps": bool(getattr(args, "anomaly_volume_maps", 0)), "volume_z_maps": bool(getattr(args, "anomaly_volume_z_maps", 0))}
+    if not any(on.values()):
+        return {}
+    flag = "--anomaly_volume_maps 1" if on["volume_maps"] else zmaps.VOLUME_FLAG
+    if int(args.spatial_dimension) != 3:
+        raise ValueError(f"{flag}: the maps of volumes need --spatial_dimension 3 (2-D images: --anomaly_maps 1 / --anomaly_z_maps 1)")
+    if (on["volume_maps"] and s["anomaly_maps"]) or (on["volume_z_maps"] and s["anomaly_z_maps"]):
+        raise ValueError(f"{flag}: not together with its 2-D counterpart (--anomaly_maps 1 / --anomaly_z_maps 1): they write the same files")
+    for name in ("pixel_metrics", "pixel_regions", "pixel_calibrate_fpr", "pixel_segment"):
+        if getattr(args, name, None):
+            raise ValueError(f"{flag}: --{name} is not built for volumes (metrics against masks, regions, calibration and "
+                             f"segmentation cover 2-D maps only)")
+    if on["volume_z_maps"]:
+        zmaps.check_volume_flags(args.spatial_dimension, s["z_sigma"], s["z_std_floor"])
+    views = getattr(args, "anomaly_volume_views", "last")
+    if views not in VOLUME_VIEWS:
+        raise ValueError(f"{flag}: --anomaly_volume_views must be one of {VOLUME_VIEWS}, got {views!r}")
+    budget_gb = float(getattr(args, "anomaly_volume_budget_gb", DEFAULT_VOLUME_BUDGET_GB))
+    if not budget_gb > 0:
+        raise ValueError(f"{flag}: --anomaly_volume_budget_gb must be positive, got {budget_gb}")
+    return dict(on, volume_views=views, volume_budget=int(budget_gb * (1 << 30)))
+
+
+def check_volume_budget(B: int, n_t: int, extent, per_t: bool, budget_bytes: int) -> int:
+    """The bytes of a batch's maps on the device -- B x 2 x D H W fp32 accumulated, with the Z-maps B x n_t x 2 x D H W for the
+    per-t stack -- or ValueError when they exceed the budget (before anything is allocated)."""
+    voxels = int(np.prod([int(e) for e in extent], dtype=np.int64))
+    need = int(B) * (int(n_t) if per_t else 1) * 2 * voxels * 4
+    if need > int(budget_bytes):
+        shape = " x ".join(str(int(e)) for e in extent)
+        raise ValueError(f"--anomaly_volume_{'z_' if per_t else ''}maps 1: the maps of a batch of {B} volumes ({B} x {n_t if per_t else 1} x 2 x "
+                         f"{shape} fp32 = {need / (1 << 30):.3f} GiB) exceed the budget of {budget_bytes / (1 << 30):.3f} GiB: lower "
+                         f"--batch_size or raise --anomaly_volume_budget_gb")
+    return need
 
 
 class RowLayout:
@@ -197,13 +256,15 @@ class MapPipeline:
     def begin(self, dataset_name: str, loader, t_values) -> "MapPass":
         return MapPass(self, dataset_name, loader, t_values)
 
-    def smooth(self, z, H: int, W: int):
-        """--anomaly_z_sigma > 0: the Z-maps [..., H, W] blurred plane by plane (one launch), else ``z`` itself."""
+    def smooth(self, z, extent):
+        """--anomaly_z_sigma > 0: the Z-maps [..., *extent] blurred plane by plane (H, W: one launch) or volume by volume (D, H, W: the
+        in-plane launch and the depth pass), else ``z`` itself."""
         if not self.s.z_sigma > 0:
             return z
         if self._taps is None:
             self._taps = torch.from_numpy(ops.gaussian_taps(self.s.z_sigma).astype(np.float32)).to(self.device)
-        return ops.map_blur(z.reshape(-1, H, W), taps=self._taps)
+        blur = ops.map_blur if len(extent) == 2 else ops.map_blur3d
+        return blur(z.reshape((-1,) + tuple(extent)), taps=self._taps)
 
     def zero_mask(self, B: int, P: int):
         """uint8 [B, P] of zeros (the in set, an out set without masks, the validation set: every pixel is a negative)."""
@@ -224,7 +285,7 @@ class MapPipeline:
         return torch.tensor([1 << b for b in range(SEG_BITS)], dtype=torch.int32, device=self.device)
 
     def tables(self, t_values, shape, fresh=False):
-        """(mean, inv_std) [n_t, 2, H, W] on the device: the statistics of this process's validation pass (``fresh``: it just
+        """(mean, inv_std) [n_t, 2, *extent] on the device: the statistics of this process's validation pass (``fresh``: it just
         ended), else those of ood/map_stats.npz (--run_val 0), which must have been written for these t-starts and this extent."""
         if fresh or self._tables is None or self._tables[0] != list(t_values) or self._tables[1].shape != shape:
             extent = tuple(shape[2:])
@@ -261,8 +322,8 @@ class MapPass:
     def __init__(self, pipeline: MapPipeline, dataset_name: str, loader, t_values):
         self.p, self.loader, self.t_values = pipeline, loader, [int(t) for t in t_values]
         s = pipeline.s
-        self.stats = zmaps.MapStats() if s.anomaly_z_maps and dataset_name == "val" else None
-        self.z_maps = s.anomaly_z_maps and dataset_name != "val"  # (the validation set gets no Z-maps)
+        self.stats = zmaps.MapStats() if s.want_z_maps and dataset_name == "val" else None
+        self.z_maps = s.want_z_maps and dataset_name != "val"  # (the validation set gets no Z-maps)
         self.counting = s.pixel_metrics and dataset_name != "val"
         self.segmenting = s.pixel_segment and dataset_name != "val"  # (the validation pass does nothing for it)
         self.seg_rows, self.seg_plane = [], None  # fp32 host rows [B, packed segmentation + integer row], one entry per batch; (H, W)
@@ -276,7 +337,7 @@ class MapPass:
         self.rows_skipped = 0  # validation images left out of the statistics (a non-finite score)
 
     def add_batch(self, scores, maps, per_t_maps, mask=None):
-        """One batch after the numeric guard: ``maps`` [B, 2, H, W] goes to the host.  ``per_t_maps`` [B, n_t, 2, H, W], validation:
+        """One batch after the numeric guard ([.., H, W] below: [.., D, H, W] for volumes): ``maps`` [B, 2, H, W] goes to the host.  ``per_t_maps`` [B, n_t, 2, H, W], validation:
         the rows whose scores are all finite go into the running statistics.  Any other pass: the batch's Z-maps and, with --pixel_metrics
         1, their counts against ``mask`` (uint8 [B, 1, H, W]; None: all zero) reach the host in ONE copy, the Z-maps as their int32 bits."""
         if maps is not None:
@@ -284,7 +345,9 @@ class MapPass:
         if per_t_maps is None:
             return
         p = self.p
-        B, n_t, _, H, W = per_t_maps.shape
+        B, n_t = per_t_maps.shape[:2]
+        extent = tuple(per_t_maps.shape[3:])
+        P1 = 2 * int(np.prod(extent, dtype=np.int64))
         if self.stats is not None:
             finite = torch.isfinite(scores).all(dim=2).all(dim=1)
             keep = int(finite.sum())
@@ -296,8 +359,12 @@ class MapPass:
             self.rows_skipped += B - keep
             return
         mean, inv_std = p.tables(self.t_values, per_t_maps.shape[1:])
-        z = ops.map_zscore(per_t_maps.reshape(B, n_t, 2 * H * W), mean.reshape(n_t, 2 * H * W), inv_std.reshape(n_t, 2 * H * W))
-        z = p.smooth(z, H, W)
+        z = ops.map_zscore(per_t_maps.reshape(B, n_t, P1), mean.reshape(n_t, P1), inv_std.reshape(n_t, P1))
+        z = p.smooth(z, extent)
+        if not (self.segmenting or self.counting):
+            self.zmaps.append(z.reshape((B, 2) + extent).cpu())
+            return
+        H, W = extent  # (the steps against masks are 2-D only: refused with the volume flags)
         if self.segmenting:
             self.segment_batch(z.reshape(B, 2, H * W), mask if self.counting else None, H, W)
         if not self.counting:
@@ -448,7 +515,7 @@ class MapPass:
         kept = []
         for per_t in rows:
             B, _, _, H, W = per_t.shape
-            z = p.smooth(ops.map_zscore_loo(per_t, mean_d, m2_d, n, floor_d), H, W).reshape(B, 2, H * W)
+            z = p.smooth(ops.map_zscore_loo(per_t, mean_d, m2_d, n, floor_d), (H, W)).reshape(B, 2, H * W)
             no_mask = p.zero_mask(B, H * W)
             for c in range(2):
                 ops.map_mask_hist(z[:, c].contiguous(), no_mask, s.px_lo, s.px_hi, s.px_bins, total=hist[c])
@@ -471,8 +538,8 @@ class MapPass:
         p, s = self.p, self.p.s
         ids, files = (local_ids, gathered_ids, name_of), {}
         t = np.asarray(self.t_values, dtype=np.int64)
-        if s.anomaly_maps:
-            got = self._gather("--anomaly_maps 1", self.maps, results, *ids)
+        if s.want_maps:
+            got = self._gather("--anomaly_volume_maps 1" if s.volume_maps else "--anomaly_maps 1", self.maps, results, *ids)
             if got is not None:
                 files[MAPS] = {"filename": np.asarray(got[0]), "t": t, "lpips_map": np.ascontiguousarray(got[1][:, 0]),
                                "mse_map": np.ascontiguousarray(got[1][:, 1])}
@@ -481,7 +548,7 @@ class MapPass:
             if s.px_calibrate:
                 files[pixel_metrics.CALIBRATION_FILE] = p.last_calibration
         if self.z_maps:
-            got = self._gather("--anomaly_z_maps 1", self.zmaps, results, *ids)
+            got = self._gather(zmaps.VOLUME_FLAG if s.volume_z_maps else zmaps.FLAG, self.zmaps, results, *ids)
             if got is not None:
                 files[ZMAPS] = {"filename": np.asarray(got[0]), "t": t, "z_lpips_map": np.ascontiguousarray(got[1][:, 0]),
                                 "z_mse_map": np.ascontiguousarray(got[1][:, 1]), "sigma": np.float64(s.z_sigma),

@@ -867,24 +867,47 @@ def map_blur(maps, sigma: float = None, taps=None, out=None):
     maps = require_device_f32(maps, "maps")
     if maps.ndim != 3 or min(maps.shape) < 1:
         raise ValueError(f"map_blur wants [N, H, W] maps, got {tuple(maps.shape)}")
-    if (sigma is None) == (taps is None):
-        raise ValueError("map_blur: give sigma or taps (one of them)")
-    if taps is None:
-        if not float(sigma) >= 0.0 or int(4.0 * float(sigma) + 0.5) > MAP_BLUR_MAX_RADIUS:
-            raise ValueError(f"map_blur: sigma = {sigma} needs radius {int(4.0 * float(sigma) + 0.5) if sigma == sigma else sigma}, "
-                             f"outside 0 .. {MAP_BLUR_MAX_RADIUS}")
-        w = gaussian_taps(sigma)
-        taps = torch.empty((len(w),), dtype=torch.float32, device=maps.device)
-        taps.copy_(torch.from_numpy(w.astype(np.float32)))
-    else:
-        taps = require_device_f32(taps, "taps")
-        if taps.ndim != 1 or taps.numel() % 2 != 1:
-            raise ValueError(f"map_blur: taps must be an odd number of weights in one row, got {tuple(taps.shape)}")
-        if taps.numel() > 2 * MAP_BLUR_MAX_RADIUS + 1:
-            raise ValueError(f"map_blur: radius {taps.numel() // 2} is above the maximum of {MAP_BLUR_MAX_RADIUS}")
+    taps = _blur_taps("map_blur", maps.device, sigma, taps)
     N, H, W = maps.shape
     out = _fresh_out(out, (N, H, W), maps.device, "map_blur")
     check(lib.ddpm_map_blur_f32(ptr(maps), ptr(out), ptr(taps), taps.numel() // 2, N, H, W, stream_ptr()), "map_blur")
+    return out
+
+
+def _blur_taps(what, device, sigma, taps):
+    """The device row of weights of ``map_blur`` / ``map_blur3d``: ``gaussian_taps(sigma)`` rounded to fp32, or the caller's."""
+    if (sigma is None) == (taps is None):
+        raise ValueError(f"{what}: give sigma or taps (one of them)")
+    if taps is None:
+        if not float(sigma) >= 0.0 or int(4.0 * float(sigma) + 0.5) > MAP_BLUR_MAX_RADIUS:
+            raise ValueError(f"{what}: sigma = {sigma} needs radius {int(4.0 * float(sigma) + 0.5) if sigma == sigma else sigma}, "
+                             f"outside 0 .. {MAP_BLUR_MAX_RADIUS}")
+        w = gaussian_taps(sigma)
+        taps = torch.empty((len(w),), dtype=torch.float32, device=device)
+        taps.copy_(torch.from_numpy(w.astype(np.float32)))
+        return taps
+    taps = require_device_f32(taps, "taps")
+    if taps.ndim != 1 or taps.numel() % 2 != 1:
+        raise ValueError(f"{what}: taps must be an odd number of weights in one row, got {tuple(taps.shape)}")
+    if taps.numel() > 2 * MAP_BLUR_MAX_RADIUS + 1:
+        raise ValueError(f"{what}: radius {taps.numel() // 2} is above the maximum of {MAP_BLUR_MAX_RADIUS}")
+    return taps
+
+
+def map_blur3d(vols, sigma: float = None, taps=None, out=None):
+    """Separable Gaussian smoothing of [N, D, H, W] volumes with scipy's mode="reflect" boundary (``gaussian_filter(vols[n],
+    sigma)``, truncate 4): the H and W passes of ``map_blur`` over the N D planes, then the depth pass.  ``sigma`` / ``taps`` /
+    ``out`` as ``map_blur``; radius <= 16 also beyond an extent, else ValueError.  Not in place (one volume-sized scratch buffer)."""
+    lib = _lib.load()
+    vols = require_device_f32(vols, "vols")
+    if vols.ndim != 4 or min(vols.shape) < 1:
+        raise ValueError(f"map_blur3d wants [N, D, H, W] volumes, got {tuple(vols.shape)}")
+    taps = _blur_taps("map_blur3d", vols.device, sigma, taps)
+    N, D, H, W = vols.shape
+    out = _fresh_out(out, (N, D, H, W), vols.device, "map_blur3d")
+    tmp = torch.empty_like(out)
+    check(lib.ddpm_map_blur3d_f32(ptr(vols), ptr(out), ptr(tmp), ptr(taps), taps.numel() // 2, N, D, H, W, stream_ptr()),
+          "map_blur3d")
     return out
 
 
@@ -1286,6 +1309,39 @@ def lpips_map_upsample(maps, layer_sizes, full_size, window=None, weight: float 
     flat = [v for s in sizes + [(0, 0)] * (5 - len(sizes)) for v in s]
     check(lib.ddpm_lpips_map_upsample_f32(ptr(maps), ptr(out), N, maps.shape[1], len(sizes), *flat, Hf, Wf, oy, ox, H, W,
                                           float(weight), acc, stream_ptr()), "lpips_map_upsample")
+    return out
+
+
+def lpips_map_upsample_view(maps, layer_sizes, volume_shape, axis: int, weight: float = 1.0, out=None):
+    """The LPIPS map of volumes from their slices along ``axis`` (2, 3 or 4 of [N, C, D, H, W]): out[n, d, h, w] (+)= weight * what
+    ``lpips_map_upsample`` gives for the voxel's slice at the voxel's place in it, written straight into the volume's layout.
+    ``maps``: [N * S, row_stride], the slices' packed rows, volume-major (S = the extent along ``axis``); ``layer_sizes``: the
+    layers of a slice's plane ([H, W], [D, W] or [D, H]); ``volume_shape`` = (D, H, W).  ``out`` given: a contiguous fp32
+    [N, D, H, W] to add into."""
+    lib = _lib.load()
+    maps = require_device_f32(maps, "maps")
+    if maps.ndim != 2:
+        raise ValueError(f"lpips_map_upsample_view: maps must be [N * S, row_stride], got {tuple(maps.shape)}")
+    sizes = [(int(h), int(w)) for h, w in layer_sizes]
+    if not 1 <= len(sizes) <= 5:
+        raise ValueError(f"lpips_map_upsample_view: 1 .. 5 layers, got {len(sizes)}")
+    if min(min(s) for s in sizes) < 1:
+        raise ValueError(f"lpips_map_upsample_view: an empty AlexNet layer in {sizes}: nothing to resample")
+    if sum(h * w for h, w in sizes) > maps.shape[1]:
+        raise ValueError(f"lpips_map_upsample_view: layers {sizes} do not fit a row of {maps.shape[1]}")
+    if int(axis) != axis or not 2 <= int(axis) <= 4:
+        raise ValueError(f"lpips_map_upsample_view: axis must be 2, 3 or 4 of [N, C, D, H, W], got {axis}")
+    shape = tuple(int(v) for v in volume_shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"lpips_map_upsample_view: volume_shape must be (D, H, W), got {tuple(volume_shape)}")
+    S = shape[int(axis) - 2]
+    if maps.shape[0] < S or maps.shape[0] % S:
+        raise ValueError(f"lpips_map_upsample_view: {maps.shape[0]} rows are no whole number of volumes of {S} slices")
+    N = maps.shape[0] // S
+    out, acc = _accumulator(out, (N,) + shape, maps.device, "lpips_map_upsample_view")
+    flat = [v for s in sizes + [(0, 0)] * (5 - len(sizes)) for v in s]
+    check(lib.ddpm_lpips_map_upsample_view_f32(ptr(maps), ptr(out), N, maps.shape[1], len(sizes), *flat, *shape, int(axis),
+                                               float(weight), acc, stream_ptr()), "lpips_map_upsample_view")
     return out
 
 

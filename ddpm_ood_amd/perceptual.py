@@ -172,18 +172,15 @@ class LPIPS(nn.Module):
         s3 = (pool(s2[0]), pool(s2[1]))
         return [s1, s2, s3, s3, s3]
 
-    def _forward_hip(self, in0, in1, normalize: bool, value: bool = True, spatial: bool = False, window=None, weight: float = 1.0,
-                     out=None, second_weight=None):
-        """(value [N, 1, 1, 1] or None, map [N, 1, H, W] or None) from ONE feature pass.  The value comes from the same
-        lpips_layer calls whether or not the map is asked for.  Map: every layer's per-position distance into one packed
-        row per pair, then one launch that resamples the five layers to the input's extent (``window`` = (oy, ox, H, W) of
-        it) and sums them, times ``weight``, into ``out`` [N, H, W] if given.  ``second_weight`` given: a third result, the
-        same packed rows resampled once more, times ``second_weight``, into a fresh [N, 1, H, W] (a second launch of the
-        resampling kernel after the first; nothing before it changes)."""
+    def _rows_hip(self, in0, in1, normalize: bool, value: bool = True, spatial: bool = False):
+        """ONE feature pass over the pairs: (value [N] or None, the packed rows [N, sum_k h_k w_k] of every layer's per-position
+        distance or None, the layers' extents or None).  The value comes from the same lpips_layer calls whether or not the rows
+        are asked for."""
         from . import ops
 
         n = in0.shape[0]
         full = tuple(in0.shape[2:])
+        sizes = None
         if spatial:
             sizes = self.pyramid_sizes(*full)
             if min(min(s) for s in sizes) < 1:
@@ -202,6 +199,21 @@ class LPIPS(nn.Module):
             if spatial:
                 ops.lpips_layer_map(f[:n], f[n:], lin, maps, offset)
                 offset += f.shape[2] * f.shape[3]
+        return val, maps, sizes
+
+    def _forward_hip(self, in0, in1, normalize: bool, value: bool = True, spatial: bool = False, window=None, weight: float = 1.0,
+                     out=None, second_weight=None):
+        """(value [N, 1, 1, 1] or None, map [N, 1, H, W] or None) from ONE feature pass.  The value comes from the same
+        lpips_layer calls whether or not the map is asked for.  Map: every layer's per-position distance into one packed
+        row per pair, then one launch that resamples the five layers to the input's extent (``window`` = (oy, ox, H, W) of
+        it) and sums them, times ``weight``, into ``out`` [N, H, W] if given.  ``second_weight`` given: a third result, the
+        same packed rows resampled once more, times ``second_weight``, into a fresh [N, 1, H, W] (a second launch of the
+        resampling kernel after the first; nothing before it changes)."""
+        from . import ops
+
+        n = in0.shape[0]
+        full = tuple(in0.shape[2:])
+        val, maps, sizes = self._rows_hip(in0, in1, normalize, value, spatial)
         if spatial:
             full_map = ops.lpips_map_upsample(maps, sizes, full, window, weight, out)
             if second_weight is not None:
@@ -284,6 +296,45 @@ class PerceptualLoss(nn.Module):
                                                                window=window, weight=weight, out=out,
                                                                second_weight=second_weight)
         return (val * self.perceptual_factor, *maps)
+
+    @torch.no_grad()
+    def forward_with_volume_map(self, y: torch.Tensor, y_pred: torch.Tensor, views: str = "last", weight: float = 1.0, out=None,
+                                second_weight=None):
+        """3-D (2.5-D) only: (the loss ``forward`` returns, bit for bit; the per-voxel map [N, 1, D, H, W]) of [N, C, D, H, W]
+        volumes.  The map of a view at a voxel is the 2-D spatial LPIPS map of the slice the voxel lies in, at the voxel's place
+        in that slice.  ``views`` = "last": the view whose value ``forward`` returns (quirk Q7: slices along the last axis);
+        "all": the mean of the maps of every view of ``fake_3d_axis`` (the feature passes of the other views run for the map
+        only).  ONE feature pass per view.  ``out`` [N, D, H, W]: the map is added into it, times ``weight``, instead of returned
+        fresh; ``second_weight`` given: a fresh second map times ``second_weight`` comes third (the same rows resampled again)."""
+        from . import ops
+
+        if self.dimensions != 3 or not self.fake_3D_views:
+            raise NotImplementedError("Volume maps are built for 3D inputs over 2.5-D views only.")
+        if self.keep_ratio != 1:
+            raise NotImplementedError("Volume maps need every slice: drop_ratio must be 0.")
+        if views not in ("last", "all"):
+            raise ValueError(f"forward_with_volume_map: views must be 'last' or 'all', got {views!r}")
+        y, y_pred = y.float(), y_pred.float()
+        if y.ndim != 5 or y.shape != y_pred.shape:
+            raise ValueError(f"forward_with_volume_map wants two equal [N, C, D, H, W] volumes, got {tuple(y.shape)} and "
+                             f"{tuple(y_pred.shape)}")
+        lp = self.perceptual_function
+        use = self.fake_3D_views if views == "all" else self.fake_3D_views[-1:]
+        share = 1.0 / len(use)
+        volume = tuple(y.shape[2:])
+        loss = second = None
+        for k, (permute_dims, view_dims) in enumerate(use):
+            ys = y.permute(*permute_dims).contiguous().view(-1, *(y.shape[d] for d in view_dims))
+            ps = y_pred.permute(*permute_dims).contiguous().view(-1, *(y_pred.shape[d] for d in view_dims))
+            lp._check(ys, ps)
+            last = k == len(use) - 1  # the view whose value reaches the caller
+            val, rows, sizes = lp._rows_hip(ys, ps, self.lpips_normalize, value=last, spatial=True)
+            if last:
+                loss = torch.mean(val.reshape(-1, 1, 1, 1)) * self.perceptual_factor
+            out = ops.lpips_map_upsample_view(rows, sizes, volume, permute_dims[1], weight * share, out)
+            if second_weight is not None:
+                second = ops.lpips_map_upsample_view(rows, sizes, volume, permute_dims[1], second_weight * share, second)
+        return (loss, out[:, None]) if second_weight is None else (loss, out[:, None], second[:, None])
 
     def _calculate_fake_3d_loss(self, y, y_pred, permute_dims, view_dims):
         ys = y.permute(*permute_dims).contiguous().view(-1, *(y.shape[d] for d in view_dims))

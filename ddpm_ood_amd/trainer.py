@@ -35,7 +35,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .data import get_data_loader
 from .map_passes import (CALIBRATED, MAPS, PIXELS, REGIONS, SEGMENTS, ZMAPS, MapPipeline, MapSettings, file_stem, gather_rows,  # noqa: F401
-                         map_rows_in_csv_order)
+                         check_volume_budget, map_rows_in_csv_order)
 from .perceptual import PerceptualLoss
 from .scheduler import DDPMScheduler, PNDMScheduler
 from .unet import DiffusionModelUNet
@@ -260,7 +260,7 @@ class Reconstruct(BaseTrainer):
             self.out_dir.mkdir(exist_ok=True)
         # the anomaly-map stack (map_passes.py): settings, what outlives a pass, and the last get_scores call's files (rank 0) for _write
         self.settings = settings
-        self.anomaly_maps, self.anomaly_z_maps = settings.anomaly_maps, settings.anomaly_z_maps
+        self.anomaly_maps, self.anomaly_z_maps = settings.want_maps, settings.want_z_maps  # (images or, DESIGN 3.29, volumes)
         self.z_sigma, self.z_std_floor = settings.z_sigma, settings.z_std_floor
         self.map_pipeline = MapPipeline(settings, self.device, self.out_dir, self.rank, self.world, self.ddp)
         self._files = {}
@@ -446,11 +446,13 @@ class Reconstruct(BaseTrainer):
         idx = batch["index"]
         per_t = []
         lp_map = se_map = None
+        if self.settings.volume:  # refused before the batch's maps are allocated
+            check_volume_budget(B, len(t_values), images_original.shape[2:], self.anomaly_z_maps, self.settings.volume_budget)
         if self.anomaly_maps:  # accumulated into once per t-start with weight 1 / n_t; no synchronisation inside the loop
             lp_map = torch.zeros((B,) + tuple(images_original.shape[2:]), dtype=torch.float32, device=self.device)
             se_map = torch.zeros_like(lp_map)
             w_t = 1.0 / max(len(t_values), 1)
-        per_t_maps = [] if self.anomaly_z_maps else None  # fresh maps of every t-start at weight 1 (2-D only)
+        per_t_maps = [] if self.anomaly_z_maps else None  # fresh maps of every t-start at weight 1
         for t_start in start_points:
             if self.reset_scheduler_per_t:
                 sched.set_timesteps(self.num_inference_steps)
@@ -481,13 +483,18 @@ class Reconstruct(BaseTrainer):
             if prof_decode:
                 _lib.load().ddpm_prof_enable(0)
             mse = ops.clamp_mse_(images_original, x, self.b_scale)  # x / b_scale, clamp_(0, 1), MSE
-            if self.anomaly_maps or self.anomaly_z_maps:  # (2-D only) the score from the launches ``pl(...)`` makes, and the maps
+            if self.anomaly_maps or self.anomaly_z_maps:  # the score from the launches ``pl(...)`` makes, and the maps
                 kw = {}
                 if self.anomaly_maps:  # accumulated; --anomaly_z_maps 1 beside it: the resampling kernel runs a second time
                     ops.sqerr_map(images_original, x, w_t, out=se_map)
                     kw = dict(weight=w_t, out=lp_map, **({"second_weight": 1.0} if self.anomaly_z_maps else {}))
-                pd_, *lp_t = self._lpips_2d(pl, images_original, x, with_map=True, **kw)
-                pd_ = pd_.reshape(B)
+                if self.settings.volume:  # per item, as the score without the flags: a volume's slices are one LPIPS batch
+                    got = [pl.forward_with_volume_map(images_original[b, None, ...], x[b, None, ...], views=self.settings.volume_views,
+                                                      **(dict(kw, out=lp_map[b:b + 1]) if kw else {})) for b in range(B)]
+                    pd_, lp_t = torch.stack([g[0].reshape(()) for g in got]), [torch.cat([g[-1] for g in got], dim=0)]
+                else:
+                    pd_, *lp_t = self._lpips_2d(pl, images_original, x, with_map=True, **kw)
+                    pd_ = pd_.reshape(B)
                 if self.anomaly_z_maps:  # this t-start's two maps, fresh
                     per_t_maps.append(torch.stack([lp_t[-1][:, 0], ops.sqerr_map(images_original, x)], dim=1))
             elif self.spatial_dimension == 2:

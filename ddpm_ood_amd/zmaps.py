@@ -18,6 +18,7 @@ from . import ops
 CHANNELS = ("lpips", "mse")
 STATS_FILE = "map_stats.npz"
 FLAG = "--anomaly_z_maps 1"
+VOLUME_FLAG = "--anomaly_volume_z_maps 1"
 
 
 def check_flags(spatial_dimension, vqvae_checkpoint, sigma: float = 0.0, rel_floor: float = 0.01):
@@ -35,16 +36,32 @@ def check_flags(spatial_dimension, vqvae_checkpoint, sigma: float = 0.0, rel_flo
         raise ValueError(f"{FLAG}: --anomaly_z_std_floor must lie in (0, 1], got {rel_floor}")
 
 
+def check_volume_flags(spatial_dimension, sigma: float = 0.0, rel_floor: float = 0.01):
+    """The same for ``--anomaly_volume_z_maps 1``: volumes only, with or without a VQ-VAE; the smoothing is 3-D."""
+    if int(spatial_dimension) != 3:
+        raise ValueError(f"{VOLUME_FLAG}: Z-maps of volumes need --spatial_dimension 3 (2-D images: {FLAG})")
+    if not float(sigma) >= 0.0:
+        raise ValueError(f"{VOLUME_FLAG}: --anomaly_z_sigma must not be negative, got {sigma}")
+    radius = int(4.0 * float(sigma) + 0.5)
+    if radius > ops.MAP_BLUR_MAX_RADIUS:
+        raise ValueError(f"{VOLUME_FLAG}: --anomaly_z_sigma {sigma} needs a radius of {radius} voxels, above the smoothing kernel's "
+                         f"maximum of {ops.MAP_BLUR_MAX_RADIUS} (sigma < 4.125)")
+    if not 0.0 < float(rel_floor) <= 1.0:
+        raise ValueError(f"{VOLUME_FLAG}: --anomaly_z_std_floor must lie in (0, 1], got {rel_floor}")
+
+
 def std_floor(std, rel_floor: float):
-    """floor[t, c] = rel_floor * the largest std of that (t, c) over the pixels, float64 [n_t, 2, 1, 1], from the fp32 std table:
+    """floor[t, c] = rel_floor * the largest std of that (t, c) over the pixels (voxels), float64 [n_t, 2, 1, 1(, 1)], from the fp32
+    std table [n_t, 2, *extent] (an image's H, W or a volume's D, H, W):
     the absolute floor of the divisor.  ``finalize_tables`` (the in / out sets) and ``MapStats.floor`` (the leave-one-out Z-maps of
     the validation set) both take it from here."""
     std = np.asarray(std, dtype=np.float32)
-    if std.ndim != 4:
+    if std.ndim not in (4, 5):
         raise ValueError(f"map statistics want a [n_t, 2, H, W] std table, got {std.shape}")
-    top = std.astype(np.float64).max(axis=(2, 3), keepdims=True)
+    top = std.astype(np.float64).max(axis=tuple(range(2, std.ndim)), keepdims=True)
     if not np.isfinite(top).all() or (top <= 0).any():
-        bad = [(int(t), CHANNELS[int(c)]) for t, c in zip(*np.nonzero(~(top[:, :, 0, 0] > 0) | ~np.isfinite(top[:, :, 0, 0])))]
+        flat = top.reshape(top.shape[:2])
+        bad = [(int(t), CHANNELS[int(c)]) for t, c in zip(*np.nonzero(~(flat > 0) | ~np.isfinite(flat)))]
         raise ValueError(f"map statistics: no pixel of (t index, channel) {bad} varies over the validation set (largest std 0 or "
                          f"not finite): nothing to normalise by")
     return float(rel_floor) * top
@@ -55,14 +72,15 @@ def finalize_tables(mean, std, rel_floor: float):
     floor[t, c] = rel_floor * the largest std of that (t, c) over the pixels, in float64, rounded once.  Both a run's own validation
     pass and a run that loads the file come through here with the same fp32 arrays, so they divide by the same bits."""
     mean, std = np.asarray(mean, dtype=np.float32), np.asarray(std, dtype=np.float32)
-    if mean.shape != std.shape or mean.ndim != 4:
+    if mean.shape != std.shape or mean.ndim not in (4, 5):
         raise ValueError(f"map statistics want two [n_t, 2, H, W] tables, got {mean.shape} and {std.shape}")
     inv = 1.0 / np.maximum(std.astype(np.float64), std_floor(std, rel_floor))
     return mean, inv.astype(np.float32)
 
 
 class MapStats:
-    """n, mean and m2 (the sum of squared deviations) of the per-t maps [n_t, 2, H, W] over the validation rows seen so far.
+    """n, mean and m2 (the sum of squared deviations) of the per-t maps [n_t, 2, H, W] over the validation rows seen so far
+    (volumes: [n_t, 2, D, H, W] throughout; every formula is per column, only the floor looks at the extent).
     Running: the two tables are device tensors, ``update`` is one kernel call.  ``from_tables`` / ``load``: host tables."""
 
     def __init__(self):
@@ -73,7 +91,7 @@ class MapStats:
     # ---- running, on the device
     def update(self, values):
         """values: [B, n_t, 2, H, W] on the device, the rows to be counted (the caller leaves non-finite images out)."""
-        if values.ndim != 5 or values.shape[2] != 2:
+        if values.ndim not in (5, 6) or values.shape[2] != 2:  # ([B, n_t, 2, D, H, W]: volumes)
             raise ValueError(f"MapStats.update wants [B, n_t, 2, H, W] values, got {tuple(values.shape)}")
         if self.mean is None:
             self.mean = torch.empty(tuple(values.shape[1:]), dtype=torch.float32, device=values.device)
@@ -137,7 +155,8 @@ class MapStats:
     def floor(self, rel_floor: float = 0.01):
         """The absolute floor of the divisor per (t, channel), fp32 [n_t, 2]: ``std_floor`` of the fp32 std, rounded once -- what
         ``ops.map_zscore_loo`` takes, and the number ``finalize`` floors the in / out sets' divisor at."""
-        return std_floor(self.std(), rel_floor)[:, :, 0, 0].astype(np.float32)
+        floor = std_floor(self.std(), rel_floor)
+        return floor.reshape(floor.shape[:2]).astype(np.float32)
 
     def save(self, path, t_values, rel_floor: float = 0.01):
         n, mean, _ = self.tables()
@@ -153,7 +172,7 @@ class MapStats:
             raise FileNotFoundError(f"{FLAG}: no validation pass in this run and no {path}: run with --run_val 1 first")
         with np.load(path) as z:
             t, n, mean, std = [int(v) for v in z["t"]], int(z["n"]), z["mean"].astype(np.float32), z["std"].astype(np.float32)
-        if mean.ndim != 4 or mean.shape != std.shape or mean.shape[:2] != (len(t), 2):
+        if mean.ndim not in (4, 5) or mean.shape != std.shape or mean.shape[:2] != (len(t), 2):
             raise ValueError(f"{path}: tables of {mean.shape} / {std.shape} for {len(t)} t-starts are no map statistics")
         if t_values is not None and [int(v) for v in t_values] != t:
             raise ValueError(f"{path} holds the t-starts {t}, this run has {[int(v) for v in t_values]}")

@@ -451,6 +451,15 @@ int ddpm_lpips_layer_map_f32(const float *f0, const float *f1, const float *lin,
 int ddpm_lpips_map_upsample_f32(const float *maps, float *out, int N, int64_t row_stride, int n_layers, int h0, int w0, int h1,
                                 int w1, int h2, int w2, int h3, int w3, int h4, int w4, int Hfull, int Wfull, int oy, int ox,
                                 int H, int W, float weight, int accumulate, ddpm_stream_t stream);
+/* The LPIPS map of volumes [N, D, H, W] from their slices along `axis` (2, 3 or 4 of [N, C, D, H, W]).  maps:
+ * [N * S, row_stride], the packed rows of the slices, volume-major, S the extent along the axis; a slice's plane is [H, W]
+ * (axis 2), [D, W] (axis 3) or [D, H] (axis 4), and the layers' extents are those of that plane.  out[n, d, h, w] =
+ * (accumulate ? out : 0) + weight * the layer sum of ddpm_lpips_map_upsample_f32 for the voxel's slice at the voxel's position
+ * in its plane (full grid, no window) -- the same expressions in the same order, written straight into the volume's layout
+ * with contiguous stores along w for every axis.  Extents 1 .. 2^20; out may not overlap maps.                              */
+int ddpm_lpips_map_upsample_view_f32(const float *maps, float *out, int N, int64_t row_stride, int n_layers, int h0, int w0,
+                                     int h1, int w1, int h2, int w2, int h3, int w3, int h4, int w4, int D, int H, int W,
+                                     int axis, float weight, int accumulate, ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Per-pixel Z-scores of the anomaly maps against the validation set (--anomaly_z_maps 1).  Entry points added
@@ -488,6 +497,13 @@ int ddpm_map_zscore_loo_f32(const float *values, const float *mean, const float 
  * negative), m < L ? m : 2L - 1 - m -- any radius up to the maximum of 16, also beyond H or W (H or W = 1 included).  One
  * launch; radius 0 with taps[0] = 1 is an exact copy; out may overlap neither in nor taps (refused: not in place).        */
 int ddpm_map_blur_f32(const float *in, float *out, const float *taps, int radius, int N, int H, int W, ddpm_stream_t stream);
+/* The same smoothing of [N, D, H, W] volumes (--anomaly_volume_z_maps 1): scipy.ndimage.gaussian_filter(vol,
+ * sigma, mode="reflect") with the one row of weights on all three axes.  Pass order, fixed: H, then W (ddpm_map_blur_f32 over
+ * the N D planes, into tmp), then D:  out[d, y, x] = sum_k taps[k] tmp[refl(d + k - radius, D), y, x], k ascending, the sum
+ * starting with its first product.  tmp: N D H W floats of scratch.  Any radius up to 16, also beyond an extent (an extent of
+ * 1 included); radius 0 with taps[0] = 1 is an exact copy.  out and tmp may overlap no other operand (refused).             */
+int ddpm_map_blur3d_f32(const float *in, float *out, float *tmp, const float *taps, int radius, int N, int D, int H, int W,
+                        ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Pixel-level evaluation of maps against ground-truth masks (--pixel_metrics 1).  Entry points added without

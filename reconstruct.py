@@ -90,6 +90,16 @@ _EXTENSIONS = [
                               "--pixel_segmented 1); planes up to 128 x 128"),
     ("pixel_median", int, 3, "--pixel_segment 1: the side of the median filter, 1 (none), 3 or 5"),
     ("pixel_min_component", int, 4, "--pixel_segment 1: predicted components of fewer pixels are removed (1 .. 16384; 1: none)"),
+    ("anomaly_volume_maps", int, 0, "1 (--spatial_dimension 3, with or without --vqvae_checkpoint): also write ood/maps_<name>.npz, "
+                                    "the per-voxel 2.5-D LPIPS and squared-error maps [N, D, H, W] of the decoded volume against "
+                                    "the input, averaged over the t-starts"),
+    ("anomaly_volume_z_maps", int, 0, "1 (--spatial_dimension 3): also write ood/map_stats.npz and ood/zmaps_<name>.npz for volumes, "
+                                      "as --anomaly_z_maps 1 does for images; --anomaly_z_sigma smooths in 3-D, "
+                                      "--anomaly_z_std_floor keeps its meaning (ood_detection.py --score zmap reads the files)"),
+    ("anomaly_volume_views", str, "last", "the slice directions the LPIPS map of a volume is taken over: last (the view whose "
+                                          "value is the perceptual_difference column) or all (the mean of the three views' maps)"),
+    ("anomaly_volume_budget_gb", float, 8.0, "the most device memory (GiB) a batch's maps of volumes may take (batch x t-starts x 2 x "
+                                             "D x H x W fp32 with --anomaly_volume_z_maps 1); a larger batch is refused"),
 ]
 
 
