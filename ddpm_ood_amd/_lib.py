@@ -168,6 +168,16 @@ SIGNATURES = {
     "ddpm_map_region_overlap_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ddpm_map_component_counts_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # ---- region-level metrics of volumes: forest in caller-provided global memory (additive: the ABI version stays)
+    "ddpm_regions3d_label_scratch_bytes": (C.c_int64, [C.c_int] * 4),
+    "ddpm_map_label3d_u8": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),
+    "ddpm_map_label3d_f32": (C.c_int, [C.c_void_p, C.c_float] + [C.c_int] * 5 + [C.c_void_p] * 4),
+    "ddpm_regions3d_overlap_scratch_bytes": (C.c_int64, [C.c_int] * 3),
+    "ddpm_map_region_overlap3d_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_int,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ddpm_regions3d_counts_scratch_bytes": (C.c_int64, [C.c_int] * 5),
+    "ddpm_map_component_counts3d_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
     # ---- predicted segmentations: median filter, size-filtered components (additive: the ABI version stays)
     "ddpm_map_median_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
     "ddpm_map_segment_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5),

@@ -20,7 +20,8 @@ non-interlaced) and binary PGM / PPM, with PILReader's axis swap -- JPEG / TIFF 
 Synthetic id specs (no dataset can be downloaded here):
     synthetic:<kind>[:n=N][:size=S][:channels=C][:seed=K][:mix=P][:name=X]
         kind in {blobs, noise, speckle (blobs + P % uniform noise), lesion (blobs with one disc of uniform noise, P % of the
-                 extent across; the disc is the ground-truth mask: ``synthetic_masks``), blobs3d, noise3d}
+                 extent across; the disc is the ground-truth mask: ``synthetic_masks``), blobs3d, noise3d, lesion3d (blobs3d
+                 with one ball of uniform noise, the ball the mask)}
 3-D volumes ([N, C, D, H, W]; ``.npy`` files of shape (D, H, W) or (C, D, H, W)) are handled with the
 same transforms (crop, area resize, min-max scale, flips of the first / second spatial axis).
 """
@@ -90,11 +91,33 @@ def _lesion(n: int, channels: int, size: int, seed: int, mix: int):
     return torch.where(inside, noise, x), inside.to(torch.uint8)
 
 
+def _lesion3d(n: int, channels: int, size: int, seed: int, mix: int):
+    """(volumes, masks uint8 [N, 1, D, H, W]) of kind "lesion3d": ``_lesion`` with a depth axis.  The min-max-scaled blobs3d of the same
+    seed with one ball per volume replaced by uniform noise; the centres and then the noise are drawn from the same generator after
+    the blobs; a centre lies in [r, size - 1 - r] on the three axes, so that the ball lies inside the volume (r = ``lesion_radius``:
+    ``mix`` percent of the extent across, at least 2 voxels).  Nothing is rescaled afterwards: outside the ball the volume is
+    ``scale_intensity(_blobs3d(...))`` bit for bit."""
+    gen = torch.Generator().manual_seed(seed)
+    x = scale_intensity(_blobs3d(n, channels, size, gen))
+    r = lesion_radius(size, mix)
+    centres = r + torch.rand(n, 3, generator=gen) * max(size - 1 - 2 * r, 0.0)
+    if size - 1 < 2 * r:  # (a ball wider than the volume: centred, cut by the border)
+        centres = torch.full((n, 3), (size - 1) / 2.0)
+    noise = torch.rand(n, channels, size, size, size, generator=gen)
+    g = torch.arange(size, dtype=torch.float32)
+    zs, ys, xs = torch.meshgrid(g, g, g, indexing="ij")
+    c = centres[:, :, None, None, None]
+    inside = ((zs[None] - c[:, 0]) ** 2 + (ys[None] - c[:, 1]) ** 2 + (xs[None] - c[:, 2]) ** 2 <= r * r)[:, None]
+    return torch.where(inside, noise, x), inside.to(torch.uint8)
+
+
 def synthetic_masks(kind: str, n: int, channels: int = 1, size: int = 32, seed: int = 0, mix: int = 10) -> torch.Tensor:
     """The ground-truth anomaly masks of ``synthetic_images`` with the same arguments: uint8 [N, 1, *spatial], 1 inside the disc
     of kind "lesion", all zero for every other kind."""
     if kind == "lesion":
         return _lesion(n, channels, size, seed, mix)[1]
+    if kind == "lesion3d":
+        return _lesion3d(n, channels, size, seed, mix)[1]
     if kind in ("blobs3d", "noise3d"):
         return torch.zeros(n, 1, size, size, size, dtype=torch.uint8)
     if kind in ("blobs", "speckle", "noise"):
@@ -108,6 +131,8 @@ def synthetic_images(kind: str, n: int, channels: int = 1, size: int = 32, seed:
     with one disc of uniform noise, ``mix`` percent of the extent across (``synthetic_masks`` has the disc)."""
     if kind == "lesion":
         return _lesion(n, channels, size, seed, mix)[0]
+    if kind == "lesion3d":
+        return _lesion3d(n, channels, size, seed, mix)[0]
     gen = torch.Generator().manual_seed(seed)
     if kind == "blobs3d":
         return scale_intensity(_blobs3d(n, channels, size, gen))

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ops, pixel_metrics, zmaps
+from . import ops, pixel_metrics, voxel_passes, zmaps
 
 # what ``MapPass.collect`` returns on rank 0: {file name with the set's name left open: the arrays of the .npz, in key order}
 MAPS, ZMAPS, PIXELS, REGIONS, CALIBRATED, SEGMENTS = (f"{kind}_{{name}}.npz" for kind in ("maps", "zmaps", "pixels", "regions", "calibrated",
@@ -239,9 +239,12 @@ def map_rows_in_csv_order(results, ids, name_of):
 class MapPipeline:
     """What outlives a pass, each built at its first use: the Z tables the in / out sets are normalised by, the smoothing taps,
     the fixed thresholds and an all-zero mask on the device, the calibration in force, and the two results of a validation pass."""
-    def __init__(self, s: MapSettings, device, out_dir, rank: int = 0, world: int = 1, ddp: bool = False):
+    def __init__(self, s: MapSettings, device, out_dir, rank: int = 0, world: int = 1, ddp: bool = False, voxel=None):
         self.s, self.device, self.out_dir, self.rank, self.world, self.ddp = s, device, Path(out_dir), rank, world, ddp
+        self.voxel = voxel if voxel is not None and voxel.metrics else None  # voxel_passes.VoxelSettings (DESIGN 3.30); None: off
         self.layout = RowLayout(len(s.px_thresholds), len(s.cal_fprs) if s.px_calibrate else 0, s.pixel_regions) if s.pixel_metrics else None
+        if self.voxel:  # (never beside --pixel_metrics 1: refused) the same row, with the voxel flags' thresholds
+            self.layout = RowLayout(len(self.voxel.thresholds), 0, self.voxel.regions)
         self.device_layout = self.layout.without("mask_pixels") if self.layout else None  # (the masks' pixel counts are taken on the host)
         self.last_map_stats = None  # (MapStats, t values) of the last validation pass, merged over the ranks
         self.last_calibration = None  # the contents of ood/calibration.npz after a validation pass with --pixel_calibrate_fpr
@@ -274,7 +277,7 @@ class MapPipeline:
 
     @functools.cached_property
     def thresholds(self):
-        return torch.tensor(self.s.px_thresholds, dtype=torch.float32, device=self.device)
+        return torch.tensor(self.voxel.thresholds if self.voxel else self.s.px_thresholds, dtype=torch.float32, device=self.device)
 
     @functools.cached_property
     def seg_thresholds(self):
@@ -325,6 +328,7 @@ class MapPass:
         self.stats = zmaps.MapStats() if s.want_z_maps and dataset_name == "val" else None
         self.z_maps = s.want_z_maps and dataset_name != "val"  # (the validation set gets no Z-maps)
         self.counting = s.pixel_metrics and dataset_name != "val"
+        self.voxel_counting = pipeline.voxel is not None and dataset_name != "val"  # --voxel_metrics 1 (voxel_passes.py)
         self.segmenting = s.pixel_segment and dataset_name != "val"  # (the validation pass does nothing for it)
         self.seg_rows, self.seg_plane = [], None  # fp32 host rows [B, packed segmentation + integer row], one entry per batch; (H, W)
         self.cal_rows = None  # --pixel_calibrate_fpr, validation: the counted rows' per-t maps, one device tensor per batch
@@ -361,6 +365,11 @@ class MapPass:
         mean, inv_std = p.tables(self.t_values, per_t_maps.shape[1:])
         z = ops.map_zscore(per_t_maps.reshape(B, n_t, P1), mean.reshape(n_t, P1), inv_std.reshape(n_t, P1))
         z = p.smooth(z, extent)
+        if self.voxel_counting:  # volumes: the Z-maps go to the host as they do without the flag, the integer row in a copy of its own
+            parts, mask_voxels = voxel_passes.count_batch(self, z.reshape(B, 2, P1 // 2), mask, extent, n_t)
+            self.zmaps.append(z.reshape((B, 2) + extent).cpu())
+            self.rows.append(p.layout.pack(dict(p.device_layout.unpack(p.device_layout.pack(parts).cpu()), mask_pixels=mask_voxels)))
+            return
         if not (self.segmenting or self.counting):
             self.zmaps.append(z.reshape((B, 2) + extent).cpu())
             return
@@ -555,6 +564,8 @@ class MapPass:
                                 "rel_floor": np.float64(s.z_std_floor)}
         if self.segmenting:
             self._collect_segments(files, t, results, *ids)
+        if self.voxel_counting:
+            return voxel_passes.collect(self, files, t, results, *ids)
         if not self.counting:
             return files
         # --pixel_metrics 1: the histogram (and the overlap table) summed over the ranks, ONE all_reduce each, and every rank's integer

@@ -1109,6 +1109,146 @@ def map_component_counts(maps, masks, labels, regions, thresholds, connectivity:
     return counts
 
 
+# ---- region-level metrics of volumes: the forest in global memory, many workgroups per volume -------
+
+MAP_LABEL3D_CONNECTIVITIES = (26, 18, 6)  # scipy.ndimage.generate_binary_structure(3, 3 | 2 | 1)
+MAP_LABEL3D_MAX_VOXELS = 2 ** 31 - 1
+MAP_OVERLAP3D_CHUNK_BYTES = 16 << 20      # the default chunk of map_region_overlap3d: regions whose histograms fill this much
+MAP_OVERLAP3D_MAX_CHUNK = 65536
+
+
+def _volumes(t, dtype, name, what):
+    """``t`` as it is, or ValueError: a contiguous [N, D, H, W] device tensor of ``dtype`` with fewer than 2^31 voxels a volume."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor on a ROCm device (no CPU fallback)")
+    if t.ndim != 4 or t.numel() == 0:
+        raise ValueError(f"{what} wants {name} of shape [N, D, H, W], got {tuple(t.shape)}")
+    if t.shape[1] * t.shape[2] * t.shape[3] > MAP_LABEL3D_MAX_VOXELS:
+        raise ValueError(f"{what}: a volume of {t.shape[1]} x {t.shape[2]} x {t.shape[3]} voxels is not below 2^31")
+    return tuple(int(v) for v in t.shape)
+
+
+def _connectivity3d(connectivity, what):
+    if isinstance(connectivity, bool) or connectivity not in MAP_LABEL3D_CONNECTIVITIES:
+        raise ValueError(f"{what}: connectivity must be 26, 18 or 6, got {connectivity!r}")
+    return int(connectivity)
+
+
+def _scratch(nbytes, device, what):
+    """The scratch of a 3-D region op: ``nbytes`` as the library's size function answers (0: it refuses the arguments)."""
+    if nbytes <= 0:
+        raise ValueError(f"{what}: the library refuses these extents (scratch size 0)")
+    return torch.empty(((int(nbytes) + 7) // 8,), dtype=torch.int64, device=device)
+
+
+def map_label3d_scratch_bytes(N: int, D: int, H: int, W: int) -> int:
+    return int(_lib.load().ddpm_regions3d_label_scratch_bytes(int(N), int(D), int(H), int(W)))
+
+
+def map_region_overlap3d_chunk(nbins: int) -> int:
+    """The default ``chunk_regions`` of ``map_region_overlap3d``."""
+    return max(1, min(MAP_OVERLAP3D_MAX_CHUNK, MAP_OVERLAP3D_CHUNK_BYTES // (4 * (int(nbins) + 2))))
+
+
+def map_region_overlap3d_scratch_bytes(N: int, nbins: int, chunk_regions: int = None) -> int:
+    chunk = map_region_overlap3d_chunk(nbins) if chunk_regions is None else int(chunk_regions)
+    return int(_lib.load().ddpm_regions3d_overlap_scratch_bytes(int(N), int(nbins), chunk))
+
+
+def map_component_counts3d_scratch_bytes(N: int, D: int, H: int, W: int, K: int) -> int:
+    return int(_lib.load().ddpm_regions3d_counts_scratch_bytes(int(N), int(D), int(H), int(W), int(K)))
+
+
+def map_label3d(x, connectivity: int = 26, threshold: float = None):
+    """``map_label`` for [N, D, H, W] volumes of any extent below 2^31 voxels: (labels int32 [N, D, H, W], regions int32 [N]),
+    the components numbered as ``scipy.ndimage.label`` numbers them with ``generate_binary_structure(3, k)``: ``connectivity``
+    26 (k = 3), 18 (k = 2) or 6 (k = 1)."""
+    lib = _lib.load()
+    what = "map_label3d"
+    connectivity = _connectivity3d(connectivity, what)
+    if threshold is None:
+        N, D, H, W = _volumes(x, torch.uint8, "x (no threshold: a mask)", what)
+    else:
+        N, D, H, W = _volumes(x, torch.float32, "x (with a threshold: a map)", what)
+    labels = torch.empty((N, D, H, W), dtype=torch.int32, device=x.device)
+    regions = torch.empty((N,), dtype=torch.int32, device=x.device)
+    scratch = _scratch(lib.ddpm_regions3d_label_scratch_bytes(N, D, H, W), x.device, what)
+    if threshold is None:
+        rc = lib.ddpm_map_label3d_u8(ptr(x), N, D, H, W, connectivity, ptr(labels), ptr(regions), ptr(scratch), stream_ptr())
+    else:
+        rc = lib.ddpm_map_label3d_f32(ptr(x), float(np.float32(threshold)), N, D, H, W, connectivity, ptr(labels), ptr(regions),
+                                      ptr(scratch), stream_ptr())
+    check(rc, what)
+    return labels, regions
+
+
+def map_region_overlap3d(maps, labels, regions, lo: float, hi: float, nbins: int, total=None, chunk_regions: int = None):
+    """``map_region_overlap`` for maps of fewer than 2^31 values an item: float64 [nbins + 1] with the same definition and the same
+    bits.  ``chunk_regions``: how many regions' histograms the scratch holds at a time (default: 16 MB worth); a volume with more
+    regions takes one pass per chunk, and the result does not depend on it.  Synchronises the stream once (it reads ``regions``)."""
+    lib = _lib.load()
+    what = "map_region_overlap3d"
+    if not isinstance(maps, torch.Tensor) or not maps.is_cuda or maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise ValueError(f"{what}: maps must be a contiguous {torch.float32} tensor on a ROCm device (no CPU fallback)")
+    if maps.ndim < 2 or maps.numel() == 0:
+        raise ValueError(f"{what} wants maps of shape [N, ...], got {tuple(maps.shape)}")
+    N, P = int(maps.shape[0]), int(maps.numel() // maps.shape[0])
+    if P > MAP_LABEL3D_MAX_VOXELS:
+        raise ValueError(f"{what}: {P} values an item are not below 2^31")
+    _labels_and_regions(labels, regions, maps.shape, maps.device, what)
+    nbins = int(nbins)
+    if not 1 <= nbins <= MAP_HIST_MAX_BINS:
+        raise ValueError(f"{what}: nbins must lie in 1 .. {MAP_HIST_MAX_BINS}, got {nbins}")
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo):
+        raise ValueError(f"{what}: the range must be finite with lo < hi, got [{lo}, {hi})")
+    chunk = map_region_overlap3d_chunk(nbins) if chunk_regions is None else int(chunk_regions)
+    if not 1 <= chunk <= MAP_OVERLAP3D_MAX_CHUNK:
+        raise ValueError(f"{what}: chunk_regions must lie in 1 .. {MAP_OVERLAP3D_MAX_CHUNK}, got {chunk_regions!r}")
+    inv_step = float(np.float32(nbins / (hi - lo)))
+    shape = (nbins + 1,)
+    if total is None:
+        total, acc = torch.empty(shape, dtype=torch.float64, device=maps.device), 0
+    elif (not isinstance(total, torch.Tensor) or tuple(total.shape) != shape or total.dtype != torch.float64
+          or not total.is_contiguous() or total.device != maps.device):
+        raise ValueError(f"{what}: total must be a contiguous float64 {shape} tensor on {maps.device}")
+    else:
+        acc = 1
+    scratch = _scratch(lib.ddpm_regions3d_overlap_scratch_bytes(N, nbins, chunk), maps.device, what)
+    check(lib.ddpm_map_region_overlap3d_f32(ptr(maps), ptr(labels), ptr(regions), N, P, float(np.float32(lo)), inv_step, nbins, chunk,
+                                            ptr(scratch), ptr(total), acc, stream_ptr()), what)
+    return total
+
+
+def map_component_counts3d(maps, masks, labels, regions, thresholds, connectivity: int = 26):
+    """``map_component_counts`` for [N, D, H, W] volumes: int32 [N, K, 3] = hit, pred, false_pred per volume and threshold."""
+    lib = _lib.load()
+    what = "map_component_counts3d"
+    connectivity = _connectivity3d(connectivity, what)
+    N, D, H, W = _volumes(maps, torch.float32, "maps", what)
+    if _volumes(masks, torch.uint8, "masks", what) != (N, D, H, W) or masks.device != maps.device:
+        raise ValueError(f"{what} wants maps and masks of one shape [N, D, H, W] on one device, got {tuple(maps.shape)} and "
+                         f"{tuple(masks.shape)}")
+    _labels_and_regions(labels, regions, maps.shape, maps.device, what)
+    if isinstance(thresholds, torch.Tensor):
+        thr = thresholds
+        if not thr.is_cuda or thr.dtype != torch.float32 or thr.ndim != 1 or not thr.is_contiguous() or thr.device != maps.device:
+            raise ValueError(f"{what}: thresholds must be a contiguous float32 [K] tensor on {maps.device}")
+    else:
+        host = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+        thr = torch.empty((len(host),), dtype=torch.float32, device=maps.device)
+        if len(host):
+            thr.copy_(torch.from_numpy(host))
+    K = int(thr.numel())
+    if not 1 <= K <= MAP_COUNTS_MAX_K:
+        raise ValueError(f"{what}: 1 .. {MAP_COUNTS_MAX_K} thresholds, got {K}")
+    counts = torch.empty((N, K, 3), dtype=torch.int32, device=maps.device)
+    scratch = _scratch(lib.ddpm_regions3d_counts_scratch_bytes(N, D, H, W, K), maps.device, what)
+    check(lib.ddpm_map_component_counts3d_f32(ptr(maps), ptr(masks), ptr(labels), ptr(regions), N, D, H, W, ptr(thr), K, connectivity,
+                                              ptr(counts), ptr(scratch), stream_ptr()), what)
+    return counts
+
+
 # ---- predicted segmentations: median filter, size-filtered components (DESIGN 3.27) -------------------------------
 
 MAP_MEDIAN_SIZES = (3, 5)

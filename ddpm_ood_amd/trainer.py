@@ -36,6 +36,7 @@ from . import _lib, ops
 from .data import get_data_loader
 from .map_passes import (CALIBRATED, MAPS, PIXELS, REGIONS, SEGMENTS, ZMAPS, MapPipeline, MapSettings, file_stem, gather_rows,  # noqa: F401
                          check_volume_budget, map_rows_in_csv_order)
+from .voxel_passes import VoxelSettings
 from .perceptual import PerceptualLoss
 from .scheduler import DDPMScheduler, PNDMScheduler
 from .unet import DiffusionModelUNet
@@ -252,6 +253,7 @@ class BaseTrainer:
 class Reconstruct(BaseTrainer):
     def __init__(self, args):
         settings = MapSettings.from_args(args)  # the extension flags' refusals come before any device, library or checkpoint
+        voxel = VoxelSettings.from_args(args)
         super().__init__(args)
         if not self.found_checkpoint:
             raise FileNotFoundError("Failed to find a saved model checkpoint.")
@@ -262,7 +264,7 @@ class Reconstruct(BaseTrainer):
         self.settings = settings
         self.anomaly_maps, self.anomaly_z_maps = settings.want_maps, settings.want_z_maps  # (images or, DESIGN 3.29, volumes)
         self.z_sigma, self.z_std_floor = settings.z_sigma, settings.z_std_floor
-        self.map_pipeline = MapPipeline(settings, self.device, self.out_dir, self.rank, self.world, self.ddp)
+        self.map_pipeline = MapPipeline(settings, self.device, self.out_dir, self.rank, self.world, self.ddp, voxel=voxel)
         self._files = {}
         self.seed = int(args.seed)
         self.num_inference_steps = int(getattr(args, "honour_num_inference_steps", 0)
@@ -562,7 +564,8 @@ class Reconstruct(BaseTrainer):
         if bool(args.run_out):
             for k, out in enumerate(args.out_ids.split(",")):
                 print(out)
-                masks = {"mask_ids": self.settings.px_masks[k]} if self.settings.pixel_metrics and self.settings.px_masks[k] else {}
+                listed = self.settings.px_masks if self.settings.pixel_metrics else self.map_pipeline.voxel.masks if self.map_pipeline.voxel else None
+                masks = {"mask_ids": listed[k]} if listed and listed[k] else {}
                 flips = {}
                 if "vflip" in out:
                     out = out.replace("_vflip", "")

@@ -560,6 +560,41 @@ int ddpm_map_component_counts_f32(const float *maps, const uint8_t *masks, const
                                   ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Region-level evaluation of maps of volumes (--voxel_regions 1): the three ops above with a depth axis.  Entry
+ * points added without an ABI bump.  Volumes [D, H, W], every extent >= 1, P = D * H * W < 2^31; connectivity 6, 18 or 26 (the
+ * three structures scipy.ndimage.generate_binary_structure(3, k)); at most 65 535 volumes (times thresholds) per call.  The
+ * union-find forest is one int32 parent per voxel in `scratch`, which the caller provides: its size in bytes comes from the
+ * _scratch_bytes function beside each entry point (int64_t; 0 for arguments the entry point refuses).  Many workgroups per volume, which
+ * communicate within a launch through device-scope integer atomics only and never wait for one another; every output element
+ * is written; no output depends on what an output or the scratch held before (but `total` with accumulate != 0), nor on the
+ * order of the atomics.  Refused with -1: a null pointer, a misaligned pointer, an output or scratch that overlaps another
+ * operand, another connectivity, an extent out of range.
+ * ---------------------------------------------------------------------------------- */
+int64_t ddpm_regions3d_label_scratch_bytes(int N, int D, int H, int W);
+/* Connected components of the voxels with mask != 0.  labels [N, D, H, W] (int32): 0 outside, else 1 .. R, the components of a
+ * volume numbered in ascending order of their smallest flat voxel index (the numbering of scipy.ndimage.label); regions [N]: R,
+ * or -1 should a bound of the lock-free unions run out (it cannot).  scratch 4-byte aligned.                                 */
+int ddpm_map_label3d_u8(const uint8_t *masks, int N, int D, int H, int W, int connectivity, int32_t *labels, int32_t *regions,
+                        void *scratch, ddpm_stream_t stream);
+/* The same for the voxels with v > thr (a NaN voxel, or a NaN thr: outside).                                                */
+int ddpm_map_label3d_f32(const float *maps, float thr, int N, int D, int H, int W, int connectivity, int32_t *labels,
+                         int32_t *regions, void *scratch, ddpm_stream_t stream);
+int64_t ddpm_regions3d_overlap_scratch_bytes(int N, int nbins, int chunk_regions);
+/* ddpm_map_region_overlap_f32 for P < 2^31: the same definition, the same additions in the same order, hence the same bits for
+ * any chunk_regions (1 .. 65 536: the regions whose integer histograms the scratch holds at a time; a volume with more regions
+ * takes one pass per chunk) and for any split of a batch with accumulate.  Copies `regions` to the host to count the chunks:
+ * the call synchronises the stream once.  scratch 8-byte aligned.                                                           */
+int ddpm_map_region_overlap3d_f32(const float *maps, const int32_t *labels, const int32_t *regions, int N, int64_t P, float lo,
+                                  float inv_step, int nbins, int chunk_regions, void *scratch, double *total, int accumulate,
+                                  ddpm_stream_t stream);
+int64_t ddpm_regions3d_counts_scratch_bytes(int N, int D, int H, int W, int K);
+/* ddpm_map_component_counts_f32 for volumes: counts [N, K, 3] = hit, pred, false_pred; a NaN threshold predicts nothing; the
+ * three counts of a (volume, threshold) are -1 should a bound of the labelling run out (it cannot).  scratch 4-byte aligned. */
+int ddpm_map_component_counts3d_f32(const float *maps, const uint8_t *masks, const int32_t *labels, const int32_t *regions, int N,
+                                    int D, int H, int W, const float *thresholds, int K, int connectivity, int32_t *counts,
+                                    void *scratch, ddpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Predicted segmentations from the maps: median filter, size-filtered components (--pixel_segment 1).  Entry
  * points added without an ABI bump; no size function (the caller allocates every buffer); every pointer but the stream is a
  * device buffer.  No global atomics, every output element written, no buffer's previous contents read.

@@ -99,7 +99,17 @@ _EXTENSIONS = [
     ("anomaly_volume_views", str, "last", "the slice directions the LPIPS map of a volume is taken over: last (the view whose "
                                           "value is the perceptual_difference column) or all (the mean of the three views' maps)"),
     ("anomaly_volume_budget_gb", float, 8.0, "the most device memory (GiB) a batch's maps of volumes may take (batch x t-starts x 2 x "
-                                             "D x H x W fp32 with --anomaly_volume_z_maps 1); a larger batch is refused"),
+                                             "D x H x W fp32 with --anomaly_volume_z_maps 1, plus the masks, labels, forests and "
+                                             "tables of --voxel_metrics 1 / --voxel_regions 1); a larger batch is refused"),
+    ("voxel_metrics", int, 0, "1 (with --spatial_dimension 3 --anomaly_volume_z_maps 1): also write ood/pixels_<name>.npz for volumes, "
+                              "the in / out sets' Z-maps against ground-truth masks voxel by voxel (--out_masks, --pixel_bins, "
+                              "--pixel_range and --pixel_thresholds keep their meaning; ood_detection.py --score pixel reads the file)"),
+    ("voxel_regions", int, 0, "1 (with --voxel_metrics 1): also write ood/regions_<name>.npz for volumes, the masks' 3-D connected "
+                              "components against the Z-maps: the per-region overlap table (AUPRO) and per-volume component counts "
+                              "(ood_detection.py --score pixel --pixel_regions 1)"),
+    ("voxel_connectivity", int, 26, "--voxel_regions 1: the neighbours that join two voxels: 26, 18 or 6 "
+                                    "(scipy.ndimage.generate_binary_structure(3, 3 | 2 | 1))"),
+    ("voxel_pro_fpr", float, 0.3, "--voxel_regions 1: the false-positive rate up to which the region-overlap curve is integrated"),
 ]
 
 
