@@ -181,6 +181,10 @@ SIGNATURES = {
     # ---- predicted segmentations: median filter, size-filtered components (additive: the ABI version stays)
     "ddpm_map_median_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
     "ddpm_map_segment_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5),
+    # ---- predicted segmentations of volumes (additive: the ABI version stays)
+    "ddpm_map_median3d_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "ddpm_regions3d_segment_scratch_bytes": (C.c_int64, [C.c_int] * 5),
+    "ddpm_map_segment3d_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 6),
     "ddpm_lpips_layer_backward_f32":(C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
     "ddpm_maxpool3s2_backward_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_int] * 4 + [C.c_void_p]),
     "ddpm_lpips_conv1_dgrad_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p]),

@@ -9,7 +9,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 JOBS="${JOBS:-4}"
 mkdir -p "${obj}"
 srcs=(api conv_mfma conv_wino conv_wino44 conv_wino44h conv_wino44r conv_d3s conv_s2h conv1x1_dma conv_direct conv_dispatch conv3d_edge linear_skinny groupnorm attention attention_fa attention_train elementwise lpips vq
-      unet_engine train_gemm train_ops simplex sampling likelihood lpips_train spectral zmaps pixel_metrics regions regions3d segment)
+      unet_engine train_gemm train_ops simplex sampling likelihood lpips_train spectral zmaps pixel_metrics regions regions3d segment3d segment)
 common=(--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wno-unused-value)
 # per-file flags: declare an array flags_<source> to add options to one translation unit, e.g.
 #   flags_attention=(-mllvm -amdgpu-mfma-vgpr-form=1)   # measured: 80 vs 86 TFLOP/s at n = 4096, not used
@@ -20,6 +20,9 @@ flags_conv_wino44r=(-fno-slp-vectorize)
 # regions, segment: the labelling reads 16-bit halves of the dwords its compare-and-swap works on
 flags_regions=(-fno-strict-aliasing)
 flags_segment=(-fno-strict-aliasing)
+# regions3d, segment3d: cc3_flatten_kernel is a kernel in a header both include, `inline` for the host side (clang notes that nvcc would not take it)
+flags_regions3d=(-Wno-cuda-compat)
+flags_segment3d=(-Wno-cuda-compat)
 pids=()
 for f in "${srcs[@]}"; do
   extra_name="flags_${f}[@]"

@@ -25,6 +25,7 @@
 // 32 KB + 16 KB + 1 KB + 2 KB + the reduction's 512 B: 52 KB, inside the 64 KB every CDNA part gives a workgroup.
 // No communication between workgroups, no global atomics, every output element written with a plain store, nothing depends
 // on what an output held before.  Should a bound of the labelling run out (it cannot), the (image, threshold)'s integers are -1.
+#include "median_common.h"
 #include "regions_common.h"
 
 namespace ddpm {
@@ -34,52 +35,6 @@ constexpr int kMedTileW = 64;
 constexpr int kMedTileH = 16;
 constexpr int kMedBlock = 256;
 constexpr int kMedRows = kMedTileH / (kMedBlock / kMedTileW);  // output rows per thread
-
-__device__ __forceinline__ uint32_t med_key(float v) {
-  const uint32_t b = __float_as_uint(v);
-  if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;  // a NaN of either sign: above +inf
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float med_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// scipy.ndimage's mode="reflect" (d c b a | a b c d | d c b a), any distance from the plane
-__device__ __forceinline__ int med_reflect(int i, int L) {
-  const int period = 2 * L;
-  int m = i % period;
-  if (m < 0) m += period;
-  return m < L ? m : period - 1 - m;
-}
-
-#define DDPM_MED_CE(a, b)              \
-  {                                    \
-    const uint32_t lo_ = min((a), (b)); \
-    (b) = max((a), (b));               \
-    (a) = lo_;                         \
-  }
-
-// the smallest of v[0 .. n - 1] to v[0], the largest to v[n - 1]
-template <int n>
-__device__ __forceinline__ void select_minmax(uint32_t *v) {
-#pragma unroll
-  for (int i = 0; i < n / 2; ++i) DDPM_MED_CE(v[i], v[n - 1 - i]);
-#pragma unroll
-  for (int i = 1; i < (n + 1) / 2; ++i) DDPM_MED_CE(v[0], v[i]);
-#pragma unroll
-  for (int i = n / 2; i < n - 1; ++i) DDPM_MED_CE(v[i], v[n - 1]);
-}
-
-// v[0 .. n - 1] hold n values of the window, n shrinking by one per step from n0; v[n0 ..] are the ones still to join, in order
-template <int n0, int n = n0>
-__device__ __forceinline__ uint32_t select_median(uint32_t *v) {
-  select_minmax<n>(v);
-  if constexpr (n == 3) {
-    return v[1];
-  } else {
-    v[0] = v[2 * n0 - n];  // (the smallest leaves, the next value takes its slot; the largest, in slot n - 1, falls out of the range)
-    return select_median<n0, n - 1>(v);
-  }
-}
 
 template <int R>
 __global__ __launch_bounds__(kMedBlock) void map_median_kernel(const float *__restrict__ in, float *__restrict__ out, int H, int W,

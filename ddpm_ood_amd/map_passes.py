@@ -113,8 +113,8 @@ def check_volume_flags(args, s) -> dict:
         raise ValueError(f"{flag}: not together with its 2-D counterpart (--anomaly_maps 1 / --anomaly_z_maps 1): they write the same files")
     for name in ("pixel_metrics", "pixel_regions", "pixel_calibrate_fpr", "pixel_segment"):
         if getattr(args, name, None):
-            raise ValueError(f"{flag}: --{name} is not built for volumes (metrics against masks, regions, calibration and "
-                             f"segmentation cover 2-D maps only)")
+            raise ValueError(f"{flag}: --{name} is not built for volumes (the --pixel_* flags cover 2-D maps only: its counterpart for "
+                             f"volumes is --voxel_{name[len('pixel_'):]})")
     if on["volume_z_maps"]:
         zmaps.check_volume_flags(args.spatial_dimension, s["z_sigma"], s["z_std_floor"])
     views = getattr(args, "anomaly_volume_views", "last")
@@ -241,10 +241,10 @@ class MapPipeline:
     the fixed thresholds and an all-zero mask on the device, the calibration in force, and the two results of a validation pass."""
     def __init__(self, s: MapSettings, device, out_dir, rank: int = 0, world: int = 1, ddp: bool = False, voxel=None):
         self.s, self.device, self.out_dir, self.rank, self.world, self.ddp = s, device, Path(out_dir), rank, world, ddp
-        self.voxel = voxel if voxel is not None and voxel.metrics else None  # voxel_passes.VoxelSettings (DESIGN 3.30); None: off
+        self.voxel = voxel if voxel is not None and voxel.active else None  # voxel_passes.VoxelSettings (DESIGN 3.30, 3.31); None: off
         self.layout = RowLayout(len(s.px_thresholds), len(s.cal_fprs) if s.px_calibrate else 0, s.pixel_regions) if s.pixel_metrics else None
-        if self.voxel:  # (never beside --pixel_metrics 1: refused) the same row, with the voxel flags' thresholds
-            self.layout = RowLayout(len(self.voxel.thresholds), 0, self.voxel.regions)
+        if self.voxel and self.voxel.metrics:  # (never beside --pixel_metrics 1: refused) the same row, with the voxel flags' thresholds
+            self.layout = RowLayout(len(self.voxel.thresholds), len(self.voxel.cal_fprs) if self.voxel.calibrate else 0, self.voxel.regions)
         self.device_layout = self.layout.without("mask_pixels") if self.layout else None  # (the masks' pixel counts are taken on the host)
         self.last_map_stats = None  # (MapStats, t values) of the last validation pass, merged over the ranks
         self.last_calibration = None  # the contents of ood/calibration.npz after a validation pass with --pixel_calibrate_fpr
@@ -253,8 +253,22 @@ class MapPipeline:
         self._tables = self._taps = self._no_mask = self._cal = None
         # --pixel_segment 1: T thresholds per channel (the fixed ones, then the calibrated ones); the integer row of an image
         self.seg_T = (len(s.sg_thresholds) + (len(s.cal_fprs) if s.px_calibrate else 0)) if s.pixel_segment else 0
+        if self.voxel and self.voxel.segment:  # --voxel_segment 1 (never beside --pixel_segment 1: refused): the same row
+            self.seg_T = len(self.voxel.thresholds) + (len(self.voxel.cal_fprs) if self.voxel.calibrate else 0)
         self.seg_layout = RowLayout(0, segments=[("pixels", (2, self.seg_T, 3)), ("components", (2, self.seg_T, 3)),
-                                                 ("removed", (2, self.seg_T, 2)), ("regions", ()), ("mask_pixels", ())]) if s.pixel_segment else None
+                                                 ("removed", (2, self.seg_T, 2)), ("regions", ()), ("mask_pixels", ())]) if self.seg_T else None
+
+    @property
+    def calibrating(self) -> bool:
+        return self.s.px_calibrate or bool(self.voxel and self.voxel.calibrate)
+
+    @property
+    def cal_grid(self):
+        """(flag, budget flag, lo, hi, bins, target rates, budget in bytes) of the calibration in force: the voxel flags' or the 2-D ones'."""
+        v, s = self.voxel, self.s
+        if v and v.calibrate:
+            return voxel_passes.CALIBRATE_FLAG, voxel_passes.BUDGET_FLAG, v.lo, v.hi, v.bins, v.cal_fprs, v.cal_budget
+        return pixel_metrics.CALIBRATE_FLAG, pixel_metrics.BUDGET_FLAG, s.px_lo, s.px_hi, s.px_bins, s.cal_fprs, s.cal_budget
 
     def begin(self, dataset_name: str, loader, t_values) -> "MapPass":
         return MapPass(self, dataset_name, loader, t_values)
@@ -281,7 +295,8 @@ class MapPipeline:
 
     @functools.cached_property
     def seg_thresholds(self):
-        return torch.tensor(self.s.sg_thresholds, dtype=torch.float32, device=self.device)
+        return torch.tensor(self.voxel.thresholds if self.voxel and self.voxel.segment else self.s.sg_thresholds, dtype=torch.float32,
+                            device=self.device)
 
     @functools.cached_property
     def seg_bit_weights(self):
@@ -308,12 +323,16 @@ class MapPipeline:
         else of ood/calibration.npz (--run_val 0), written with this run's t-starts, range, bins, smoothing, floor and target rates."""
         s, cal = self.s, self.last_calibration
         if fresh or self._cal is None or [int(t) for t in self._cal["t"]] != [int(t) for t in t_values]:
+            flag, _, lo, hi, bins, fprs, _ = self.cal_grid
             if cal is not None and [int(t) for t in cal["t"]] != [int(t) for t in t_values]:
-                raise ValueError(f"--pixel_calibrate_fpr: the validation pass calibrated on t = {[int(t) for t in cal['t']]}"
+                raise ValueError(f"{flag}: the validation pass calibrated on t = {[int(t) for t in cal['t']]}"
                                  f", this set has t = {list(t_values)}")
             if cal is None:
-                cal = pixel_metrics.load_calibration(self.out_dir / pixel_metrics.CALIBRATION_FILE, t_values, s.px_lo, s.px_hi,
-                                                     s.px_bins, s.z_sigma, s.z_std_floor, s.cal_fprs)
+                try:
+                    cal = pixel_metrics.load_calibration(self.out_dir / pixel_metrics.CALIBRATION_FILE, t_values, lo, hi,
+                                                         bins, s.z_sigma, s.z_std_floor, fprs)
+                except (ValueError, FileNotFoundError) as e:  # (the file and its checks are shared; the message names the flag in force)
+                    raise type(e)(str(e).replace(pixel_metrics.CALIBRATE_FLAG, flag)) from None
             self._cal = dict(cal, thr=torch.from_numpy(np.ascontiguousarray(cal["thresholds"], dtype=np.float32)).to(self.device))
         return self._cal
 
@@ -328,13 +347,16 @@ class MapPass:
         self.stats = zmaps.MapStats() if s.want_z_maps and dataset_name == "val" else None
         self.z_maps = s.want_z_maps and dataset_name != "val"  # (the validation set gets no Z-maps)
         self.counting = s.pixel_metrics and dataset_name != "val"
-        self.voxel_counting = pipeline.voxel is not None and dataset_name != "val"  # --voxel_metrics 1 (voxel_passes.py)
+        self.voxel_counting = pipeline.voxel is not None and pipeline.voxel.metrics and dataset_name != "val"  # --voxel_metrics 1 (voxel_passes.py)
+        self.voxel_segmenting = pipeline.voxel is not None and pipeline.voxel.segment and dataset_name != "val"  # --voxel_segment 1
         self.segmenting = s.pixel_segment and dataset_name != "val"  # (the validation pass does nothing for it)
         self.seg_rows, self.seg_plane = [], None  # fp32 host rows [B, packed segmentation + integer row], one entry per batch; (H, W)
         self.cal_rows = None  # --pixel_calibrate_fpr, validation: the counted rows' per-t maps, one device tensor per batch
-        if s.px_calibrate and self.stats is not None:  # they stay on the device for the leave-one-out pass: refuse first
-            shape = tuple(loader.images[0].shape) if len(loader.names) else (0, 0)
-            pixel_metrics.check_budget(len(loader.names), len(self.t_values), shape[-2], shape[-1], s.cal_budget)
+        if pipeline.calibrating and self.stats is not None:  # they stay on the device for the leave-one-out pass: refuse first
+            dims = 3 if s.volume else 2
+            shape = tuple(loader.images[0].shape) if len(loader.names) else (0,) * dims
+            flag, budget_flag, *_, budget = pipeline.cal_grid
+            pixel_metrics.check_budget(len(loader.names), len(self.t_values), *shape[-dims:], budget, flags=(flag, budget_flag))
             self.cal_rows = []
         self.hist = self.overlap = None  # int64 [2, 2, nbins + 1] / float64 [2, nbins + 1], on the device
         self.maps, self.zmaps, self.rows = [], [], []  # host tensors, one entry per batch
@@ -365,10 +387,15 @@ class MapPass:
         mean, inv_std = p.tables(self.t_values, per_t_maps.shape[1:])
         z = ops.map_zscore(per_t_maps.reshape(B, n_t, P1), mean.reshape(n_t, P1), inv_std.reshape(n_t, P1))
         z = p.smooth(z, extent)
-        if self.voxel_counting:  # volumes: the Z-maps go to the host as they do without the flag, the integer row in a copy of its own
-            parts, mask_voxels = voxel_passes.count_batch(self, z.reshape(B, 2, P1 // 2), mask, extent, n_t)
+        if self.voxel_counting or self.voxel_segmenting:  # volumes: the Z-maps go to the host as they do without the flags, the integer rows in copies of their own
+            voxel_passes.check_budget(B, n_t, extent, p.voxel, p.s.volume_budget)
+            truth = None
+            if self.voxel_counting:
+                parts, mask_voxels, truth = voxel_passes.count_batch(self, z.reshape(B, 2, P1 // 2), mask, extent, n_t)
+                self.rows.append(p.layout.pack(dict(p.device_layout.unpack(p.device_layout.pack(parts).cpu()), mask_pixels=mask_voxels)))
+            if self.voxel_segmenting:
+                voxel_passes.segment_batch(self, z.reshape(B, 2, P1 // 2), mask if self.voxel_counting else None, extent, truth)
             self.zmaps.append(z.reshape((B, 2) + extent).cpu())
-            self.rows.append(p.layout.pack(dict(p.device_layout.unpack(p.device_layout.pack(parts).cpu()), mask_pixels=mask_voxels)))
             return
         if not (self.segmenting or self.counting):
             self.zmaps.append(z.reshape((B, 2) + extent).cpu())
@@ -506,30 +533,38 @@ class MapPass:
         stats = zmaps.MapStats.from_tables(n, mean, m2, self.t_values)
         p.last_map_stats = (stats, self.t_values)
         p.tables(self.t_values, mean.shape, fresh=True)  # (n < 2 or a channel that never varies: refused here, on every rank alike)
-        if p.s.px_calibrate:
+        if p.calibrating:
             self._calibrate(stats)
 
     def _calibrate(self, stats):
         """Every rank uploads the merged mean and M2 (float64 rounded once to fp32) and the floor, bins the leave-one-out Z-maps of the
         rows it kept (smoothed like every other set's) per channel; ONE all_reduce of the int64 table: the same thresholds everywhere."""
         p, s = self.p, self.p.s
+        flag, _, lo, hi, bins, fprs, _ = p.cal_grid
         rows, self.cal_rows = self.cal_rows, None
         n, mean, m2 = stats.tables()
         if n < 3:
-            raise ValueError(f"--pixel_calibrate_fpr: leaving one of {n} validation image(s) out leaves fewer than 2: at least 3 are needed")
+            raise ValueError(f"{flag}: leaving one of {n} validation image(s) out leaves fewer than 2: at least 3 are needed")
         mean_d = torch.from_numpy(mean.astype(np.float32)).to(p.device)
         m2_d = torch.from_numpy(m2.astype(np.float32)).to(p.device)
         floor_d = torch.from_numpy(stats.floor(s.z_std_floor)).to(p.device)
-        hist = torch.zeros((2, 2, s.px_bins + 1), dtype=torch.int64, device=p.device)  # [channel, class, bin]: class 1 stays 0
+        hist = torch.zeros((2, 2, bins + 1), dtype=torch.int64, device=p.device)  # [channel, class, bin]: class 1 stays 0
         kept = []
         for per_t in rows:
-            B, _, _, H, W = per_t.shape
-            z = p.smooth(ops.map_zscore_loo(per_t, mean_d, m2_d, n, floor_d), (H, W)).reshape(B, 2, H * W)
-            no_mask = p.zero_mask(B, H * W)
-            for c in range(2):
-                ops.map_mask_hist(z[:, c].contiguous(), no_mask, s.px_lo, s.px_hi, s.px_bins, total=hist[c])
-            if s.keep_calibration_rows:
-                kept.append((per_t.cpu(), z.reshape(B, 2, H, W).cpu()))
+            extent = tuple(per_t.shape[3:])
+            P = int(np.prod(extent, dtype=np.int64))
+            # planes: the batch in one call.  Volumes: slices of rows whose Z-maps, the blur's intermediate and result and one channel's
+            # copy (3.5 x 2 D H W fp32 a row) stay inside --anomaly_volume_budget_gb, one row at the least
+            step = per_t.shape[0] if len(extent) == 2 else max(1, int(s.volume_budget // (28 * P)))
+            for r0 in range(0, per_t.shape[0], step):
+                part = per_t[r0:r0 + step]
+                B = part.shape[0]
+                z = p.smooth(ops.map_zscore_loo(part, mean_d, m2_d, n, floor_d), extent).reshape(B, 2, P)
+                no_mask = p.zero_mask(B, P)
+                for c in range(2):
+                    ops.map_mask_hist(z[:, c].contiguous(), no_mask, lo, hi, bins, total=hist[c])
+                if s.keep_calibration_rows:
+                    kept.append((part.cpu(), z.reshape((B, 2) + extent).cpu()))
         hist = hist[:, 0].contiguous()
         if p.ddp:
             hist = host_if_gloo(hist)
@@ -537,8 +572,10 @@ class MapPass:
         if s.keep_calibration_rows:
             p.calibration_rows = torch.cat([k[0] for k in kept]).numpy() if kept else None
             p.calibration_zmaps = torch.cat([k[1] for k in kept]).numpy() if kept else None
-        p.last_calibration = pixel_metrics.calibration_tables(hist.cpu().numpy(), self.t_values, n, s.cal_fprs, s.px_lo, s.px_hi,
-                                                              s.px_bins, s.z_sigma, s.z_std_floor)
+        try:
+            p.last_calibration = pixel_metrics.calibration_tables(hist.cpu().numpy(), self.t_values, n, fprs, lo, hi, bins, s.z_sigma, s.z_std_floor)
+        except ValueError as e:  # (--pixel_range is shared; the message leads with the flag in force)
+            raise ValueError(str(e).replace(pixel_metrics.CALIBRATE_FLAG, flag)) from None
         p.calibration(self.t_values, fresh=True)
 
     def collect(self, results, local_ids, gathered_ids, name_of) -> dict:
@@ -554,7 +591,7 @@ class MapPass:
                                "mse_map": np.ascontiguousarray(got[1][:, 1])}
         if self.stats is not None and p.rank == 0:  # t [n_t], n, mean / std fp32 [n_t, 2, H, W] (the un-floored std), channels, rel_floor
             files[zmaps.STATS_FILE] = lambda path, stats=p.last_map_stats[0]: stats.save(path, self.t_values, s.z_std_floor)
-            if s.px_calibrate:
+            if p.calibrating:
                 files[pixel_metrics.CALIBRATION_FILE] = p.last_calibration
         if self.z_maps:
             got = self._gather(zmaps.VOLUME_FLAG if s.volume_z_maps else zmaps.FLAG, self.zmaps, results, *ids)
@@ -564,6 +601,8 @@ class MapPass:
                                 "rel_floor": np.float64(s.z_std_floor)}
         if self.segmenting:
             self._collect_segments(files, t, results, *ids)
+        if self.voxel_segmenting:
+            voxel_passes.collect_segments(self, files, t, results, *ids)
         if self.voxel_counting:
             return voxel_passes.collect(self, files, t, results, *ids)
         if not self.counting:

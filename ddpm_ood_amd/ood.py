@@ -191,6 +191,11 @@ def score_pixels(out_npz, in_npz=None, key: str = "z_mse_map", regions_npz=None,
     return out
 
 
+# the flags of reconstruct.py that write the same files for volumes: a missing file names both
+VOXEL_FLAGS = {"--pixel_metrics 1": "--voxel_metrics 1", "--pixel_regions 1": "--voxel_regions 1",
+               "--pixel_calibrate_fpr": "--voxel_calibrate_fpr", "--pixel_segment 1": "--voxel_segment 1"}
+
+
 def _need(path, flag):
     path = Path(path)
     if not path.exists():
@@ -213,9 +218,10 @@ def score_pixels_calibrated(out_dir, out_name, key: str = "z_mse_map", regions: 
     c = pm.KEYS.index(key)
     out_dir = Path(out_dir)
     cal = pm.load_calibration(out_dir / pm.CALIBRATION_FILE)
-    px_out = _need(out_dir / f"pixels_{out_name}.npz", pm.FLAG)
-    px_in = _need(out_dir / "pixels_in.npz", pm.FLAG)
-    done = _need(out_dir / f"calibrated_{out_name}.npz", f"{pm.CALIBRATE_FLAG} with {pm.FLAG}")
+    both = lambda flag: f"{flag} (volumes: {VOXEL_FLAGS[flag]})"  # noqa: E731
+    px_out = _need(out_dir / f"pixels_{out_name}.npz", both(pm.FLAG))
+    px_in = _need(out_dir / "pixels_in.npz", both(pm.FLAG))
+    done = _need(out_dir / f"calibrated_{out_name}.npz", f"{both(pm.CALIBRATE_FLAG)} with {both(pm.FLAG)}")
     grid = (float(cal["lo"]), float(cal["hi"]), int(cal["nbins"]))
     for name, z in ((f"pixels_{out_name}.npz", px_out), ("pixels_in.npz", px_in)):
         if (float(z["lo"]), float(z["hi"]), int(z["nbins"])) != grid:
@@ -276,7 +282,8 @@ def score_segments(out_npz, in_npz=None, key: str = "z_mse_map"):
                 or any(int(zi[k]) != int(z[k]) for k in ("median", "min_component", "connectivity")):
             raise ValueError("score_segments: the in set was segmented at other thresholds or with another filter")
         seg = np.asarray(zi["segmentation"])[:, c]
-        in_fpr = np.asarray(zi["pixels"])[:, c, :, 1].astype(np.float64).sum(axis=0) / float(seg.shape[0] * seg.shape[2] * seg.shape[3])
+        # (seg: [N, T, H, W], or [N, T, D, H, W] of volumes: every pixel or voxel of the N items)
+        in_fpr = np.asarray(zi["pixels"])[:, c, :, 1].astype(np.float64).sum(axis=0) / float(seg.shape[0] * np.prod(seg.shape[2:], dtype=np.int64))
     rows = []
     for j in range(pixels.shape[1]):
         row = {"threshold": float(thresholds[j]), "fpr": float(fpr[j]), "mean_dice": float(mean_dice[j]), "pooled_dice": float(pooled_dice[j]),
@@ -292,8 +299,9 @@ def print_segments(model, o, out_dir, key):
     """``--pixel_segmented 1``: one line per threshold of ``score_segments`` for the out set ``o``."""
     from . import pixel_metrics as pm
 
-    out = _need(out_dir / f"segments_{o}.npz", pm.SEGMENT_FLAG)
-    rows = score_segments(out, _need(out_dir / "segments_in.npz", pm.SEGMENT_FLAG), key)
+    flag = f"{pm.SEGMENT_FLAG} (volumes: {VOXEL_FLAGS[pm.SEGMENT_FLAG]})"
+    out = _need(out_dir / f"segments_{o}.npz", flag)
+    rows = score_segments(out, _need(out_dir / "segments_in.npz", flag), key)
     print(f"Segmentations for {model} vs {o}: median {int(out['median'])}, components below {int(out['min_component'])} pixels removed "
           f"(connectivity {int(out['connectivity'])})")
     for r in rows:

@@ -1313,6 +1313,73 @@ def map_segment(maps, masks, labels, regions, thresholds, min_size: int, connect
     return seg, pixels, components, removed
 
 
+# ---- predicted segmentations of volumes --------------------------------------------------------------
+
+MAP_MEDIAN3D_SIZES = (3,)
+MAP_SEGMENT3D_MAX_MIN_SIZE = (1 << 31) - 1
+
+
+def map_median3d(vols, size: int = 3, out=None):
+    """The 3 x 3 x 3 median (``size`` 3, else ValueError) of [N, D, H, W] fp32 volumes, every extent >= 1:
+    ``scipy.ndimage.median_filter(vols[n], size=3, mode="reflect")`` for NaN-free input; with NaN, element 13 of ``np.sort`` of the
+    window (a NaN above +inf).  The output is an input value (the sign of a zero among equal zeros and a NaN's payload are not
+    pinned); on D = 1 volumes it has the bits of ``map_median(size=3)``.  ``out``: a contiguous fp32 [N, D, H, W] to write into; it
+    may not overlap ``vols`` (not in place)."""
+    lib = _lib.load()
+    what = "map_median3d"
+    N, D, H, W = _volumes(vols, torch.float32, "vols", what)
+    if isinstance(size, bool) or size not in MAP_MEDIAN3D_SIZES:
+        raise ValueError(f"{what}: size must be 3, got {size!r}")
+    out = _fresh_out(out, (N, D, H, W), vols.device, what)
+    check(lib.ddpm_map_median3d_f32(ptr(vols), ptr(out), int(size), N, D, H, W, stream_ptr()), what)
+    return out
+
+
+def map_segment3d_scratch_bytes(N: int, D: int, H: int, W: int, K: int) -> int:
+    return int(_lib.load().ddpm_regions3d_segment_scratch_bytes(int(N), int(D), int(H), int(W), int(K)))
+
+
+def map_segment3d(maps, masks, labels, regions, thresholds, min_size: int, connectivity: int = 26):
+    """``map_segment`` for [N, D, H, W] volumes of fewer than 2^31 voxels: connectivity 26, 18 or 6, ``min_size`` 1 .. 2^31 - 1,
+    ``labels`` / ``regions`` as ``map_label3d(masks)`` returns them.  Returns, on the device, (seg uint8 [N, K, D, H, W], pixels int32
+    [N, K, 3], components int32 [N, K, 3], removed int32 [N, K, 2]).  At ``min_size`` 1: ``map_mask_counts`` and
+    ``map_component_counts3d``."""
+    lib = _lib.load()
+    what = "map_segment3d"
+    connectivity = _connectivity3d(connectivity, what)
+    N, D, H, W = _volumes(maps, torch.float32, "maps", what)
+    if _volumes(masks, torch.uint8, "masks", what) != (N, D, H, W) or masks.device != maps.device:
+        raise ValueError(f"{what} wants maps and masks of one shape [N, D, H, W] on one device, got {tuple(maps.shape)} and "
+                         f"{tuple(masks.shape)}")
+    _labels_and_regions(labels, regions, maps.shape, maps.device, what)
+    try:
+        whole = not isinstance(min_size, bool) and int(min_size) == min_size and 1 <= int(min_size) <= MAP_SEGMENT3D_MAX_MIN_SIZE
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise ValueError(f"{what}: min_size must be an integer in 1 .. {MAP_SEGMENT3D_MAX_MIN_SIZE}, got {min_size!r}")
+    if isinstance(thresholds, torch.Tensor):
+        thr = thresholds
+        if not thr.is_cuda or thr.dtype != torch.float32 or thr.ndim != 1 or not thr.is_contiguous() or thr.device != maps.device:
+            raise ValueError(f"{what}: thresholds must be a contiguous float32 [K] tensor on {maps.device}")
+    else:
+        host = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+        thr = torch.empty((len(host),), dtype=torch.float32, device=maps.device)
+        if len(host):
+            thr.copy_(torch.from_numpy(host))
+    K = int(thr.numel())
+    if not 1 <= K <= MAP_COUNTS_MAX_K:
+        raise ValueError(f"{what}: 1 .. {MAP_COUNTS_MAX_K} thresholds, got {K}")
+    seg = torch.empty((N, K, D, H, W), dtype=torch.uint8, device=maps.device)
+    pixels = torch.empty((N, K, 3), dtype=torch.int32, device=maps.device)
+    components = torch.empty((N, K, 3), dtype=torch.int32, device=maps.device)
+    removed = torch.empty((N, K, 2), dtype=torch.int32, device=maps.device)
+    scratch = _scratch(lib.ddpm_regions3d_segment_scratch_bytes(N, D, H, W, K), maps.device, what)
+    check(lib.ddpm_map_segment3d_f32(ptr(maps), ptr(masks), ptr(labels), ptr(regions), N, D, H, W, ptr(thr), K, int(min_size), connectivity,
+                                     ptr(seg), ptr(pixels), ptr(components), ptr(removed), ptr(scratch), stream_ptr()), what)
+    return seg, pixels, components, removed
+
+
 # ---- LPIPS-AlexNet pieces (src/losses/perceptual_loss.py:105-186) -------------------------------------
 
 def lpips_conv(x, weight, bias, stride: int, pad: int, relu: bool = True, in_scale=None, in_shift=None):

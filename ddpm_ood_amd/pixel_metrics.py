@@ -220,14 +220,19 @@ def check_calibration_flags(anomaly_z_maps, fprs, budget_gb=DEFAULT_BUDGET_GB):
     return parse_fprs(fprs), int(budget * (1 << 30))
 
 
-def check_budget(rows: int, n_t: int, H: int, W: int, budget_bytes: int):
-    """The bytes of the validation rows a rank keeps on the device for the leave-one-out pass (rows x n_t x 2 x H x W fp32), or
-    ValueError when they exceed the budget."""
-    need = int(rows) * int(n_t) * 2 * int(H) * int(W) * 4
+def check_budget(rows: int, n_t: int, *extent_and_budget, flags=(CALIBRATE_FLAG, BUDGET_FLAG)):
+    """``check_budget(rows, n_t, H, W, budget_bytes)``, or ``(rows, n_t, D, H, W, budget_bytes)`` for volumes: the bytes of the
+    validation rows a rank keeps on the device for the leave-one-out pass (rows x n_t x 2 x the extent, fp32), or ValueError when
+    they exceed the budget.  ``flags``: the calibration flag and its budget flag the message names."""
+    *extent, budget_bytes = extent_and_budget
+    if len(extent) < 2:
+        raise TypeError("check_budget(rows, n_t, *extent, budget_bytes): an extent of two or three numbers")
+    need = int(rows) * int(n_t) * 2 * int(np.prod([int(e) for e in extent], dtype=object)) * 4
     if need > int(budget_bytes):
-        raise ValueError(f"{CALIBRATE_FLAG}: keeping the per-t maps of {rows} validation images ({rows} x {n_t} x 2 x {H} x {W} fp32 "
+        shape = " x ".join(str(int(e)) for e in extent)
+        raise ValueError(f"{flags[0]}: keeping the per-t maps of {rows} validation images ({rows} x {n_t} x 2 x {shape} fp32 "
                          f"= {need / (1 << 30):.3f} GiB on this rank) exceeds the budget of {budget_bytes / (1 << 30):.3f} GiB: raise "
-                         f"{BUDGET_FLAG}, use more ranks or truncate the set with --first_n_val")
+                         f"{flags[1]}, use more ranks or truncate the set with --first_n_val")
     return need
 
 

@@ -619,6 +619,32 @@ int ddpm_map_segment_f32(const float *maps, const uint8_t *masks, const int32_t 
                          int32_t *components, int32_t *removed, ddpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Predicted segmentations from the maps of volumes: the two ops above with a depth axis.  Entry points added
+ * without an ABI bump.  Volumes [D, H, W], every extent >= 1, P = D * H * W < 2^31.
+ * ---------------------------------------------------------------------------------- */
+/* out[n, z, y, x] = element 13 of the ascending sort of the 27 values of maps in the 3 x 3 x 3 window centred at (z, y, x); size
+ * must be 3 (anything else: -1); maps, out: [N, D, H, W] fp32.  The volume is extended on all three axes as scipy.ndimage does
+ * with mode="reflect" (the reflection repeats where an extent is 1 or 2); the order is np.sort's: -inf < finite < +inf < NaN.  The
+ * output is the selected input value: the sign of a zero among equal zeros and the payload of a NaN are not pinned.  On a D = 1
+ * volume: ddpm_map_median_f32(size = 3) of the plane.  Not in place: out may not overlap maps (refused), both 4-byte aligned. */
+int ddpm_map_median3d_f32(const float *maps, float *out, int size, int N, int D, int H, int W, ddpm_stream_t stream);
+int64_t ddpm_regions3d_segment_scratch_bytes(int N, int D, int H, int W, int K);
+/* ddpm_map_segment_f32 for volumes: connectivity 6, 18 or 26, 1 <= K <= 8, N * K <= 65 535, min_size 1 .. 2^31 - 1; labels /
+ * regions as ddpm_map_label3d_u8 leaves them for the masks.
+ *   seg [N, K, D, H, W] uint8  1 on the voxels of the components of {v > thr[k]} with at least min_size voxels, 0 elsewhere
+ *   pixels [N, K, 3] int32     TP, FP, FN of seg against mask != 0
+ *   components [N, K, 3]       hit (regions with a kept voxel), pred (kept components), false_pred (kept, no masked voxel)
+ *   removed [N, K, 2]          the components and the voxels the size filter dropped
+ * At min_size = 1: ddpm_map_mask_counts_f32, ddpm_map_component_counts3d_f32, removed = 0, seg = (v > thr).  The forest and one
+ * int32 size counter per voxel live in `scratch` (4-byte aligned; ddpm_regions3d_segment_scratch_bytes, 0 for arguments the entry
+ * point refuses); integer atomics only, no output depends on their order nor on what the scratch or an output held; every
+ * output element is written.  Should a bound of the labelling run out (it cannot), that pair's integers are -1.  Refused with
+ * -1: what ddpm_map_component_counts3d_f32 refuses, min_size < 1, an output or the scratch overlapping another operand.       */
+int ddpm_map_segment3d_f32(const float *maps, const uint8_t *masks, const int32_t *labels, const int32_t *regions, int N, int D,
+                           int H, int W, const float *thresholds, int K, int min_size, int connectivity, uint8_t *seg,
+                           int32_t *pixels, int32_t *components, int32_t *removed, void *scratch, ddpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Loss terms of VQ-VAE training (src/trainers/vqvae_trainer.py: 0.001 x PerceptualLoss + JukeboxLoss in the generator loss;
  * SURVEY.md A.8).  Entry points added without an ABI bump.  Everything is deterministic (fixed-order sums, no atomics).
  * ---------------------------------------------------------------------------------- */

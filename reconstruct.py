@@ -100,16 +100,29 @@ _EXTENSIONS = [
                                           "value is the perceptual_difference column) or all (the mean of the three views' maps)"),
     ("anomaly_volume_budget_gb", float, 8.0, "the most device memory (GiB) a batch's maps of volumes may take (batch x t-starts x 2 x "
                                              "D x H x W fp32 with --anomaly_volume_z_maps 1, plus the masks, labels, forests and "
-                                             "tables of --voxel_metrics 1 / --voxel_regions 1); a larger batch is refused"),
+                                             "tables of --voxel_metrics 1 / --voxel_regions 1 / --voxel_segment 1); a larger batch is refused"),
     ("voxel_metrics", int, 0, "1 (with --spatial_dimension 3 --anomaly_volume_z_maps 1): also write ood/pixels_<name>.npz for volumes, "
                               "the in / out sets' Z-maps against ground-truth masks voxel by voxel (--out_masks, --pixel_bins, "
                               "--pixel_range and --pixel_thresholds keep their meaning; ood_detection.py --score pixel reads the file)"),
     ("voxel_regions", int, 0, "1 (with --voxel_metrics 1): also write ood/regions_<name>.npz for volumes, the masks' 3-D connected "
                               "components against the Z-maps: the per-region overlap table (AUPRO) and per-volume component counts "
                               "(ood_detection.py --score pixel --pixel_regions 1)"),
-    ("voxel_connectivity", int, 26, "--voxel_regions 1: the neighbours that join two voxels: 26, 18 or 6 "
+    ("voxel_connectivity", int, 26, "--voxel_regions 1, --voxel_segment 1: the neighbours that join two voxels: 26, 18 or 6 "
                                     "(scipy.ndimage.generate_binary_structure(3, 3 | 2 | 1))"),
     ("voxel_pro_fpr", float, 0.3, "--voxel_regions 1: the false-positive rate up to which the region-overlap curve is integrated"),
+    ("voxel_calibrate_fpr", str, None, "--pixel_calibrate_fpr for volumes (with --spatial_dimension 3 --anomaly_volume_z_maps 1): comma list "
+                                       "of 1 .. 8 target false-positive rates in (0, 1); writes ood/calibration.npz from the validation "
+                                       "volumes' leave-one-out Z-maps and, with --voxel_metrics 1, ood/calibrated_<name>.npz "
+                                       "(ood_detection.py --score pixel --pixel_calibrated 1); --run_val 0 reads the file"),
+    ("voxel_calibrate_budget_gb", float, 8.0, "--voxel_calibrate_fpr: the most device memory (GiB per rank) the validation volumes' "
+                                              "per-t maps may take while they wait for the leave-one-out pass"),
+    ("voxel_segment", int, 0, "1 (with --spatial_dimension 3 --anomaly_volume_z_maps 1): also write ood/segments_<name>.npz for volumes, a "
+                              "predicted segmentation per volume, channel and threshold (--pixel_thresholds, then those of "
+                              "--voxel_calibrate_fpr): the Z-map median-filtered, thresholded, its 3-D components below a minimum size "
+                              "removed (--voxel_connectivity), with its voxel and component counts against the masks of "
+                              "--voxel_metrics 1 --out_masks if there are any (ood_detection.py --score pixel --pixel_segmented 1)"),
+    ("voxel_median", int, 3, "--voxel_segment 1: the side of the 3-D median filter, 1 (none) or 3"),
+    ("voxel_min_component", int, 8, "--voxel_segment 1: predicted components of fewer voxels are removed (1 .. 2^31 - 1; 1: none)"),
 ]
 
 
