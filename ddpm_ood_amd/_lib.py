@@ -332,6 +332,15 @@ def status_text(word: int) -> str:
     return "; ".join(t for b, t in STATUS_BITS.items() if word & b) or "clean"
 
 
+_SWITCH_GENERATION = 0
+
+
+def switch_state():
+    """What a memoised dispatcher answer (ddpm_conv_takes_wino44h, ...) has to be keyed on: (how often reload_env parsed the
+    DDPM_* switches again, the master switch as the library holds it now -- read back, so a direct ddpm_set_split_f16 counts)."""
+    return _SWITCH_GENERATION, split_f16()
+
+
 def set_split_f16(on: bool) -> bool:
     """False: every split-f16 kernel family runs its fp32-MFMA form.  Returns the previous setting."""
     return bool(load().ddpm_set_split_f16(int(bool(on))))
@@ -349,5 +358,7 @@ def split_f16_active() -> bool:
 
 def reload_env() -> None:
     """Parse the DDPM_* switches again (the library reads them once per process)."""
+    global _SWITCH_GENERATION
+    _SWITCH_GENERATION += 1
     if _LIB is not None:
         _LIB.ddpm_reload_env()

@@ -88,6 +88,8 @@ class NativeUNetStep:
         if self.loss_scale is None and not self.scale_adaptive:
             self.loss_scale = 1.0
         self._w44_cache = {}           # (input shape, couts) -> does the dispatcher take the F(4x4) kernel
+        self._w44_state = None         # the switch state (_lib.switch_state) those answers were given under
+        self._scale_exp = None         # floor(log2(elements of the batch / 2)) the adaptive loss_scale belongs to
         self._scaled = False           # the running backward's gradients are scaled into f16's range
         self.overflow_retries = 0      # backward passes repeated at a lower scale
         self.fp32_dgrad_steps = 0      # steps whose input gradients fell back to the fp32 pipe
@@ -166,6 +168,14 @@ class NativeUNetStep:
         return ops.conv(x, w, b, chan_add=chan_add, residual=residual)
 
     def _takes_wino44h(self, x_shape, cout):
+        # (the answer depends on the run-time switches, and the reconstruction guard flips them in this process: a stale True packs
+        # only the F(4x4) form and the dispatcher drops to the plain direct kernel, a stale False never takes F(4x4) again)
+        from . import _lib
+
+        state = _lib.switch_state()
+        if state != self._w44_state:
+            self._w44_cache.clear()
+            self._w44_state = state
         key = (x_shape, cout)
         if key not in self._w44_cache:
             self._w44_cache[key] = ops.conv_takes_wino44h(x_shape, cout)
@@ -491,30 +501,50 @@ class NativeUNetStep:
 
     SCALE_GROWTH_INTERVAL = 2000  # clean steps after which the adaptive scale doubles (gradients shrink as training converges)
 
+    def _fit_scale(self, numel: int) -> None:
+        """The adaptive scale for a batch of `numel` predicted elements.  dpred = 2 (pred - target) / n: n / 2 brings it to the
+        error's own magnitude; the gradients further down are smaller still (2^8 more was measured safe at batch 4 .. 256 -- and
+        the overflow check is what makes a guess harmless).  The scale FOLLOWS the element count: a ragged last batch or a change
+        of batch size moves it by the same power of two as n, so what the overflow retries and the regrowth have learnt is kept
+        relative to the batch (a scale fixed from the first batch was 2^4 too small / too large between batch 4 and 64)."""
+        e = math.floor(math.log2(max(numel / 2, 1)))
+        if self.loss_scale is None:
+            self.loss_scale = 2.0 ** (e + 8)
+        elif self._scale_exp is not None and e != self._scale_exp:
+            self.loss_scale = max(self.loss_scale * 2.0 ** (e - self._scale_exp), 1.0)
+        self._scale_exp = e
+
     def loss_and_grads(self, noisy, timesteps, target):
         """F.mse_loss(model(noisy, timesteps), target) and every parameter gradient; returns the loss as a 1-element device tensor.
 
         The backward runs on dpred * loss_scale (a power of two) and the flat gradient buffer is unscaled afterwards; the unscale
         pass flags non-finite values in the device status word, which is read here (one 4-byte read-back per step: the trainer
         reads the loss every step anyway).  Overflow (the scale pushed an input-gradient operand past f16): the scale drops by
-        2^4 and the backward runs again on the same tape -- twice at most, then once with the input gradients on the fp32 pipe; a
-        gradient that is still non-finite is a genuine one and is left in place, as the reference would."""
+        2^4 and the backward runs again on the same tape -- twice at most, then once with the input gradients on the fp32 pipe.
+        A GENUINELY non-finite gradient is none of the scale's business: a non-finite loss (a NaN batch, a forward overflow) is
+        recognised before the first repeat -- one backward pass, the scale and its clean-step count untouched --, and a gradient
+        that is still non-finite on the fp32 pipe gives back the scale and the count the step started with.  Either way the
+        non-finite gradient is left in place, as the reference would (never the previous step's finite one)."""
         from . import _lib
 
         pred = self.forward(noisy, timesteps)
         loss, dpred0 = T.mse_loss_grad(pred, target)
-        if self.scale_adaptive and self.loss_scale is None:
-            # dpred = 2 (pred - target) / n: n / 2 brings it to the error's own magnitude; the gradients further down are smaller
-            # still (2^11 more was measured safe at batch 4 .. 256 -- and the overflow check below is what makes a guess harmless)
-            self.loss_scale = 2.0 ** (math.floor(math.log2(max(pred.numel() / 2, 1))) + 8)
+        if self.scale_adaptive:
+            self._fit_scale(pred.numel())
         tape, form = self._tape, self.dgrad_form
+        start = (self.loss_scale, self._clean_steps)
+        genuine = False
         for attempt in range(4):  # (a bit left in the word by something else costs one spurious repeat)
             scale = self.loss_scale if self.dgrad_form == "wino44h" or not self.scale_adaptive else 1.0
             dpred = dpred0 if scale == 1.0 else T.axpby(dpred0, None, scale, 0.0)
             self._tape, self._scaled = tape, scale >= 1024.0
             self.backward(dpred)
             T.scale_check_(self.gflat, 1.0 / scale)
-            if not (_lib.status_read(clear=True) & _lib.STATUS_NONFINITE_GRAD) or not self.scale_adaptive or attempt == 3:
+            if not (_lib.status_read(clear=True) & _lib.STATUS_NONFINITE_GRAD) or not self.scale_adaptive:
+                break
+            # (read only on a flagged step) the loss is finite iff every prediction and target is: no scale mends those
+            if attempt == 3 or (attempt == 0 and not math.isfinite(float(loss))):
+                genuine = True
                 break
             self.overflow_retries += 1
             self._clean_steps = 0
@@ -524,7 +554,9 @@ class NativeUNetStep:
                 self.dgrad_form = "wino"  # this step only
                 self.fp32_dgrad_steps += 1
         self.dgrad_form = form
-        if self.scale_adaptive:
+        if genuine:
+            self.loss_scale, self._clean_steps = start
+        elif self.scale_adaptive:
             self._clean_steps += 1
             if self._clean_steps >= self.SCALE_GROWTH_INTERVAL:
                 self.loss_scale, self._clean_steps = self.loss_scale * 2.0, 0
@@ -547,11 +579,18 @@ class NativeUNetStep:
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
                  "params": list(range(len(self.params)))}
-        return {"state": state, "param_groups": [group]}
+        sd = {"state": state, "param_groups": [group]}
+        if self.scale_adaptive and self.loss_scale is not None:
+            # (a key torch.optim.Adam.load_state_dict does not look at) what the overflow retries and the regrowth have learnt
+            sd["loss_scale"] = {"scale": self.loss_scale, "exp": self._scale_exp, "clean_steps": self._clean_steps}
+        return sd
 
     def load_state_dict(self, sd):
         if not sd or not sd.get("state"):
             return
+        ls = sd.get("loss_scale")
+        if ls and self.scale_adaptive:
+            self.loss_scale, self._scale_exp, self._clean_steps = float(ls["scale"]), ls["exp"], int(ls["clean_steps"])
         steps = set()
         for i, p in enumerate(self.params):
             st = sd["state"].get(i)
