@@ -133,6 +133,11 @@ struct ProfScope {
   }
 };
 
+// ReLU and running maximum with torch's NaN rule (F.relu(nan) = nan, F.max_pool2d keeps a NaN of its window): fmaxf returns
+// the OTHER operand for a NaN, which would turn an overflow (inf - inf) into a finite wrong value behind every ReLU
+__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float max_keep_nan(float m, float v) { return (v > m || v != v) ? v : m; }
+
 __device__ __forceinline__ float silu_f(float v) { return v / (1.0f + expf(-v)); }
 // v_exp_f32 / v_rcp_f32 form (~1e-7 relative): 6 instructions instead of ~45
 __device__ __forceinline__ float silu_fast(float v) {

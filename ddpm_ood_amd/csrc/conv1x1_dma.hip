@@ -291,7 +291,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_dma_kernel(const ddpm_conv_des
           if constexpr (F16X3) v *= 1.f / kF16WScale;
           if (a.bias || a.chan_add) v += add[r];
           if (a.residual) v += rv[r];
-          if (a.out_act == DDPM_ACT_RELU) v = fmaxf(v, 0.f);
+          if (a.out_act == DDPM_ACT_RELU) v = relu_f(v);
           a.out[obase + (size_t)dco * HW] = v;
         }
       }

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void conv3d_k4s2_cin1_kernel(const float *__re
 #pragma unroll
     for (int k = 0; k < 64; ++k) acc = fmaf(v[k], wc[k], acc);
     if (bias) acc += bias[co];
-    dst[(size_t)co * npos] = relu ? fmaxf(acc, 0.f) : acc;
+    dst[(size_t)co * npos] = relu ? relu_f(acc) : acc;
   }
 }
 
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void convnd_generic_kernel(const float *__rest
       }
     }
     if (residual) acc += residual[i];
-    out[i] = relu ? fmaxf(acc, 0.f) : acc;
+    out[i] = relu ? relu_f(acc) : acc;
   }
 }
 

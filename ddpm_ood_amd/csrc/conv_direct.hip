@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ddpm_conv_desc a
           v = up ? plane[(hv >> 1) * a.Wi + (wv >> 1)] : plane[hv * a.Wi + wv];
           if (a.gscale) v = v * sc + sh;
           if (a.act == DDPM_ACT_SILU) v = silu_fast(v);
-          if (a.act == DDPM_ACT_RELU) v = fmaxf(v, 0.f);
+          if (a.act == DDPM_ACT_RELU) v = relu_f(v);
         }
         const int t = kh * a.ksize + kw;
 #pragma unroll
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ddpm_conv_desc a
       if (a.bias) v += a.bias[co];
       if (a.chan_add) v += a.chan_add[(size_t)n * a.chan_add_stride + co];
       if (a.residual) v += a.residual[idx];
-      if (a.out_act == DDPM_ACT_RELU) v = fmaxf(v, 0.f);
+      if (a.out_act == DDPM_ACT_RELU) v = relu_f(v);
       a.out[idx] = v;
     }
   }
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void conv_smallco_kernel(const ddpm_conv_desc 
             v = pre[j][c];
             if (a.gscale) v = v * psc[c] + psh[c];
             if (a.act == DDPM_ACT_SILU) v = silu_fast(v);
-            if (a.act == DDPM_ACT_RELU) v = fmaxf(v, 0.f);
+            if (a.act == DDPM_ACT_RELU) v = relu_f(v);
           }
           tile[c * PS + r] = v;
         }
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void conv_smallco_kernel(const ddpm_conv_desc 
     if (a.bias) v += a.bias[co];
     if (a.chan_add) v += a.chan_add[(size_t)n * a.chan_add_stride + co];
     if (a.residual) v += a.residual[idx];
-    if (a.out_act == DDPM_ACT_RELU) v = fmaxf(v, 0.f);
+    if (a.out_act == DDPM_ACT_RELU) v = relu_f(v);
     a.out[idx] = v;
   }
 }
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(64 * NWV) void conv_smallco_wave_kernel(const ddpm_
           v = pre[slot][j];
           if (a.gscale) v = v * psc[slot] + psh[slot];
           if (a.act == DDPM_ACT_SILU) v = silu_fast(v);
-          if (a.act == DDPM_ACT_RELU) v = fmaxf(v, 0.f);
+          if (a.act == DDPM_ACT_RELU) v = relu_f(v);
         }
         pl[r] = v;
       }
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(64 * NWV) void conv_smallco_wave_kernel(const ddpm_
       if (a.bias) v += a.bias[co];
       if (a.chan_add) v += a.chan_add[(size_t)n * a.chan_add_stride + co];
       if (a.residual) v += a.residual[idx];
-      if (a.out_act == DDPM_ACT_RELU) v = fmaxf(v, 0.f);
+      if (a.out_act == DDPM_ACT_RELU) v = relu_f(v);
       a.out[idx] = v;
     }
   }

@@ -579,7 +579,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(const ddpm_conv_desc 
         yy[0] += ra[rr][0]; yy[1] += ra[rr][1]; yy[2] += rb[rr][0]; yy[3] += rb[rr][1];
         if (D3 && a.out_act == DDPM_ACT_RELU) {
 #pragma unroll
-          for (int x = 0; x < 4; ++x) yy[x] = fmaxf(yy[x], 0.f);
+          for (int x = 0; x < 4; ++x) yy[x] = relu_f(yy[x]);
         }
         if (n < g.NIMG) {
           const size_t o = obase + (size_t)((rr & 3) + 8 * (rr >> 2)) * cstr;

@@ -697,7 +697,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino44_kernel(const ddpm_conv_des
           at4(w[kk][0], w[kk][1], w[kk][2], w[kk][3], w[kk][4], w[kk][5], y);
           v4f o = v4f{y[0] + ad, y[1] + ad, y[2] + ad, y[3] + ad};
           if (RES) o += res[k];
-          if (D3 && a.out_act == DDPM_ACT_RELU) o = v4f{fmaxf(o[0], 0.f), fmaxf(o[1], 0.f), fmaxf(o[2], 0.f), fmaxf(o[3], 0.f)};
+          if (D3 && a.out_act == DDPM_ACT_RELU) o = v4f{relu_f(o[0]), relu_f(o[1]), relu_f(o[2]), relu_f(o[3])};
           if (n < g.NIMG) *reinterpret_cast<v4f *>(outp + obase + (size_t)k * a.Wo) = o;
         }
       };

@@ -836,7 +836,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino44r_kernel(const ddpm_conv_de
           v4f o = v4f{__builtin_fmaf(y[0], kOutScale, ad), __builtin_fmaf(y[1], kOutScale, ad),
                       __builtin_fmaf(y[2], kOutScale, ad), __builtin_fmaf(y[3], kOutScale, ad)};
           if (RES) o += res[k];
-          if (D3 && a.out_act == DDPM_ACT_RELU) o = v4f{fmaxf(o[0], 0.f), fmaxf(o[1], 0.f), fmaxf(o[2], 0.f), fmaxf(o[3], 0.f)};
+          if (D3 && a.out_act == DDPM_ACT_RELU) o = v4f{relu_f(o[0]), relu_f(o[1]), relu_f(o[2]), relu_f(o[3])};
           if (n < g.NIMG) *reinterpret_cast<v4f *>(outp + obase + (size_t)k * a.Wo) = o;
           if (emit_stats) {
             if (k == 0) st_p = o[0];

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void lpips_conv_kernel(const float *__restrict
   }
 #pragma unroll
   for (int j = 0; j < kLpCob; ++j)
-    if (co0 + j < Cout) out[((size_t)n * Cout + co0 + j) * HWo + p] = relu ? fmaxf(acc[j], 0.f) : acc[j];
+    if (co0 + j < Cout) out[((size_t)n * Cout + co0 + j) * HWo + p] = relu ? relu_f(acc[j]) : acc[j];
 }
 
 __global__ __launch_bounds__(256) void maxpool3s2_kernel(const float *__restrict__ in, float *__restrict__ out,
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void maxpool3s2_kernel(const float *__restrict
 #pragma unroll
   for (int a = 0; a < 3; ++a)
 #pragma unroll
-    for (int b = 0; b < 3; ++b) m = fmaxf(m, src[a * W + b]);
+    for (int b = 0; b < 3; ++b) m = max_keep_nan(m, src[a * W + b]);  // F.max_pool2d keeps a NaN of its window
   out[i] = m;
 }
 
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(kL5Threads) void lpips_conv_mfma_kernel(const float
         for (int r = 0; r < 16; ++r) {
           const int co = cb * 32 + 8 * (r >> 2) + 4 * lhi + (r & 3);
           const float v = acc[t][r] + (bias ? bias[co] : 0.f);
-          out[((size_t)n * Cout + co) * HW + p] = relu ? fmaxf(v, 0.f) : v;
+          out[((size_t)n * Cout + co) * HW + p] = relu ? relu_f(v) : v;
         }
       }
     }

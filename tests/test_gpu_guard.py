@@ -207,4 +207,118 @@ def test_genuine_overflow_is_written_as_nan_like_the_reference(device, tmp_path,
     h = hip_scores(args, rec, ids, "in")
     assert rec.last_stats["batches_rerun_fp32"] == 1 and rec.last_stats["batches_nonfinite"] == 1
     assert h["mse"].isna().all()
+    assert h["perceptual_difference"].isna().all()  # (the LPIPS network's ReLUs and max-pools keep a NaN, like torch's)
     assert "genuine overflow" in capfd.readouterr().err
+
+
+# ---- the guard with a MIXED batch: one bad image between two good ones ----------------------------------------------------
+
+def _edited_loader(args, ids, edit):
+    """loader_for(...) with image 1 changed by `edit` (a copy: the cached images of other loaders stay as they are)."""
+    from parity_util import loader_for
+
+    loader = loader_for(args, ids)
+    assert torch.is_tensor(loader.images) and loader.images.shape[0] == 3
+    loader.images = loader.images.clone()
+    if edit is not None:
+        edit(loader.images[1])
+    return loader
+
+
+def _oracle_rows(args, rec, loader, model):
+    """parity_util.oracle_scores over a given loader."""
+    import oracle
+    from ddpm_ood_amd.trainer import batch_noise
+
+    pl = oracle.PerceptualLoss(dimensions=2, include_pixel_loss=False, is_fake_3d=False, lpips_normalize=True)
+    pl.perceptual_function.load_state_dict(rec._perceptual().perceptual_function.state_dict())
+    return pd.DataFrame(oracle.get_scores(
+        loader, "in", args.inference_skip_factor, model=model, vqvae=oracle.PassthroughVQVAE(), perceptual=pl, spatial_dimension=2,
+        noise_fn=lambda batch, t, shape: batch_noise(args.seed, batch["index"], t, shape), prediction_type=args.prediction_type,
+        beta_schedule=args.beta_schedule, beta_start=args.beta_start, beta_end=args.beta_end, b_scale=args.b_scale,
+        snr_shift=args.snr_shift, latent_pad=args.latent_pad, num_inference_steps=rec.num_inference_steps,
+        timestep_list=rec.timestep_list, max_t_start=rec.max_t_start, t_start_subset=getattr(rec, "t_start_subset", None)))
+
+
+def _mixed_batch_setup(tmp_path, monkeypatch):
+    import oracle
+    from ddpm_ood_amd import synthetic
+    from ddpm_ood_amd.trainer import MODEL_CONFIGS, Reconstruct
+
+    monkeypatch.setenv("DDPM_CONV_D3S", "0")  # (as in test_trainer_reruns_an_overflowing_batch_on_fp32_products)
+    ids = "synthetic:blobs:n=3:seed=21"
+    args = make_args(tmp_path, inference_skip_factor=64, batch_size=3, validation_ids=ids, in_ids=ids)
+    sd = synthetic.random_state_dict("small", 1, seed=1)
+    write_checkpoint(tmp_path, args, sd)
+    rec = Reconstruct(args)
+    rec.quiet = True
+    rec.max_t_start = 10  # 2 forwards per image
+    ref = oracle.DiffusionModelUNet(2, 1, 1, **MODEL_CONFIGS["small"]).eval()
+    ref.load_state_dict(sd)
+    return ids, args, rec, ref
+
+
+def _rows_of(df, image):
+    """The rows of the image at position `image` of the single batch of three (row order: per t, per image)."""
+    names = list(dict.fromkeys(df["filename"]))
+    assert len(names) == 3
+    return df[df["filename"] == names[image]].reset_index(drop=True)
+
+
+def test_trainer_reruns_only_the_overflowing_image_of_a_mixed_batch(device, tmp_path, capfd, monkeypatch):
+    """len(bad) < B: image 1 of a batch of three is scaled by 3e4 (beyond the f16 range of the kernels that read the raw residual
+    stream), images 0 and 2 are ordinary.  The guard runs image 1 alone again on the fp32-MFMA kernels and scatters its scores
+    back; the first-pass scores of images 0 and 2 are kept and are, bit for bit, what the same run gives with a clean image 1
+    ("a per-image result does not depend on the batch it rides in", trainer.py::get_scores)."""
+    from ddpm_ood_amd import _lib
+
+    ids, args, rec, ref = _mixed_batch_setup(tmp_path, monkeypatch)
+    scale = lambda img: img.mul_(3e4)  # noqa: E731
+    clean = pd.DataFrame(rec.get_scores(_edited_loader(args, ids, None), "in", args.inference_skip_factor))
+    assert rec.last_stats["batches_rerun_fp32"] == 0 and rec.last_stats["batches_nonfinite"] == 0, rec.last_stats
+    capfd.readouterr()
+    h = pd.DataFrame(rec.get_scores(_edited_loader(args, ids, scale), "in", args.inference_skip_factor))
+    err = capfd.readouterr().err
+    st = rec.last_stats
+    print(st)
+    assert st["batches_rerun_fp32"] == 1 and st["images_rerun_fp32"] == 1 and st["batches_nonfinite"] == 0, st
+    assert "running 1 image(s) again" in err
+    assert _lib.split_f16() is True and _lib.status_read() == 0
+    for i in (0, 2):
+        a, b = _rows_of(h, i), _rows_of(clean, i)
+        assert list(a["t"]) == list(b["t"])
+        for col in ("mse", "perceptual_difference"):
+            assert (a[col].to_numpy() == b[col].to_numpy()).all(), (i, col, a[col].to_numpy(), b[col].to_numpy())
+    o = _oracle_rows(args, rec, _edited_loader(args, ids, scale), ref)
+    assert o["mse"].notna().all()
+    assert_rows_close(_rows_of(h, 1), _rows_of(o, 1), 1e-3, "image 1, second pass")
+
+
+def test_trainer_keeps_a_nan_image_of_a_mixed_batch_nan_and_its_neighbours_exact(device, tmp_path, capfd, monkeypatch):
+    """One NaN pixel in image 1: both of its score columns are NaN at every t like the oracle's (torch.clamp_, the ReLUs and the
+    max-pools of the LPIPS network all keep a NaN), with fp32 products too (a genuine non-finite input); images 0 and 2 are
+    untouched."""
+    from ddpm_ood_amd import _lib
+
+    ids, args, rec, ref = _mixed_batch_setup(tmp_path, monkeypatch)
+
+    def nan_pixel(img):
+        img[0, 13, 17] = float("nan")
+
+    clean = pd.DataFrame(rec.get_scores(_edited_loader(args, ids, None), "in", args.inference_skip_factor))
+    h = pd.DataFrame(rec.get_scores(_edited_loader(args, ids, nan_pixel), "in", args.inference_skip_factor))
+    st = rec.last_stats
+    print(st)
+    assert "genuine overflow" in capfd.readouterr().err
+    assert st["images_rerun_fp32"] == 1 and st["batches_nonfinite"] == 1 and st["batches_rerun_fp32"] == 1, st
+    assert _lib.split_f16() is True and _lib.status_read() == 0
+    o = _oracle_rows(args, rec, _edited_loader(args, ids, nan_pixel), ref)
+    o1, h1 = _rows_of(o, 1), _rows_of(h, 1)
+    assert len(h1) == len(o1) >= 1 and list(h1["t"]) == list(o1["t"])
+    for col in ("mse", "perceptual_difference"):
+        assert o1[col].isna().all(), (col, o1[col].to_numpy())  # the reference's own behaviour
+        assert h1[col].isna().all(), (col, h1[col].to_numpy())
+    for i in (0, 2):
+        a, b = _rows_of(h, i), _rows_of(clean, i)
+        for col in ("mse", "perceptual_difference"):
+            assert (a[col].to_numpy() == b[col].to_numpy()).all(), (i, col)

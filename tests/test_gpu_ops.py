@@ -655,7 +655,7 @@ WINO_CASES = [
     (3, 256, 0, 256, 16, True, False, True),
     (5, 256, 256, 256, 8, True, True, False),     # 4 images per workgroup, ragged last workgroup
     (1, 128, 0, 64, 64, False, False, False),     # W = 64: two tile rows per workgroup, Cout = 64
-    (2, 8, 0, 64, 4, False, False, True),         # 4x4 images: 16 per workgroup
+    (2, 8, 0, 64, 4, False, False, True),         # 4x4 images: 16 per workgroup is more than the kernel stages (wino_geom) -> direct kernel
 ]
 
 
